@@ -14,11 +14,16 @@ per step) and the per-N values form a STRONG-scaling curve.  `--global-batch 0` 
 synthetic tensors of the reference's shapes (the licensed ROMP.pkl / SMPL_NEUTRAL.pth cannot be shipped); arithmetic is
 float32-accurate end to end (convs as f16x2-split products with f32 accumulation; `mesh_max_abs_vs_oracle` reports it).
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).  After the timed region rank 0 additionally
-measures (a) the per-kernel-class roofline with HIP events on the launch stream, (b) parity of the timed batch against the
-oracle (maps, detections, meshes), (c) the same job end to end from uint8 host frames (H2D + device pre-processing inside the
-timed region), (d) the same job with conv_math=f32, (e) the single-image latency of the drop-in API and (f) the CPU baseline (the oracle restatement of the reference, timed on the host cores of this box on a
-bounded sample of the same workload).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).  A plain run does only what that line's headline
+needs: set-up, the un-counted pre-heat and --warmup steps, exactly --steps timed steps, then the line.  With `--full`, rank 0
+additionally measures after the timed region (a) the per-kernel-class roofline with HIP events on the launch stream, (b) parity
+of the timed batch against the oracle (maps, detections, meshes), (c) the same job end to end from uint8 host frames (H2D +
+device pre-processing inside the timed region), (d) the same job with conv_math=f32, (e) the single-image latency of the drop-in
+API and (f) the CPU baseline (the oracle restatement of the reference, timed on the host's cores on a bounded sample of the
+same workload), and samples engine clock / socket power during the timed steps; the --no-* options switch single legs off.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in its last timed step as DIR/<name>.npy (float32; integer
+arrays as float64), before the line is printed.  Inputs and weights are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import ctypes as C
@@ -82,7 +87,51 @@ def parse_args():
     ap.add_argument('--preheat-cap', type=float, default=10.0,
                     help='seconds: UNcounted pre-heat steps in front of --warmup until two consecutive steps agree within 1 %% '
                          '(a fresh box runs its first steps slowly); 0: none.  The timed region stays exactly --steps steps')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every leg beyond the headline (roofline, oracle parity, end-to-end, f32 '
+                         'companion, single-image latency, CPU baseline) and sample clock / power; the --no-* options still apply')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
+    args = ap.parse_args()
+    if not args.full:                    # a plain run: the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_parity = args.no_end_to_end = True
+        args.no_f32_companion = args.no_latency = True
+    return args
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """Write `arrays` ({name: tensor or array}) as outdir/<name>.npy: float64 stays float64, other floats become float32, integer
+    and boolean arrays float64.  Over DUMP_LIMIT_BYTES in all (files included), the arrays whose first dimension is the largest
+    one (the per-person rows) are cut to one fixed, seeded sample of rows, whose indices go to outdir/sample_rows.npy.
+    -> {name: shape}."""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        keep64 = a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating)
+        out[k] = np.ascontiguousarray(a, dtype=np.float64 if keep64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    budget = DUMP_LIMIT_BYTES - 128 * (len(out) + 1)      # (less one .npy header per file)
+    if total > budget:
+        n = max(a.shape[0] for a in out.values() if a.ndim)
+        rows = [k for k, a in out.items() if a.ndim and a.shape[0] == n]
+        row_bytes = sum(out[k].nbytes for k in rows) / n
+        rest = total - row_bytes * n
+        k_rows = int((budget - rest - 8 * n) // row_bytes)
+        if k_rows < 1:
+            raise RuntimeError('--dump-outputs: the outputs do not fit %d MB even as a sample' % (DUMP_LIMIT_BYTES >> 20))
+        pick = np.sort(np.random.RandomState(seed).choice(n, min(n, k_rows), replace=False))
+        for k in rows:
+            out[k] = np.ascontiguousarray(out[k][pick])
+        out['sample_rows'] = pick.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(outdir, k + '.npy'), a)
+    return {k: list(a.shape) for k, a in out.items()}
 
 
 # ------------------------------------------------------------------------------------------------ roofline
@@ -395,7 +444,7 @@ def bench_smpl(args, dev):
     for _ in range(max(args.warmup, 3)):
         v, j, _ = smpl(betas, poses)
     torch.cuda.synchronize(dev)
-    steps = max(args.steps, 50)
+    steps = args.steps
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
@@ -445,6 +494,8 @@ def bench_smpl(args, dev):
             res['cpu_baseline'] = dict(value=round(N * n / cdt, 1), unit='meshes/s', cores=torch.get_num_threads(), kind='port',
                                        sample='%d calls of the torch-CPU restatement of smpl.py lbs at N=64' % n)
         res['config']['verts_max_abs_vs_oracle'] = float(np.abs(v.cpu().numpy() - vo).max())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'verts': v, 'joints': j})
     print(json.dumps(res), flush=True)
 
 
@@ -517,6 +568,8 @@ def bench_bev(args, dev):
         n = 0 if r is None else r['cam'].shape[0]
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {} if r is None else {k: v for k, v in r.items() if torch.is_tensor(v) or hasattr(v, 'dtype')})
     res = {'metric': 'images/sec (512x512, BEV HRNet-32)', 'value': round(args.batch * args.steps / dt, 2),
            'unit': 'images/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
            'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
@@ -768,12 +821,14 @@ def collective_info(world, dev):
     return info
 
 
-def run_job(args, model, images, lo, rank, world, dev, D, sensors=None):
+def run_job(args, model, images, lo, rank, world, dev, D, sensors=None, last=None):
     """The timed job of the headline line: every rank walks its resident shard in calls of --batch images (net + parse + SMPL);
     N > 1: one all-gather of the per-person records per step.  -> (seconds for args.steps steps (max over ranks), persons,
-    timing record: per-step times, the pre-heat's steps)."""
+    timing record: per-step times, the pre-heat's steps).  `last` (a dict): receives under 'records' what the last step handed
+    back, as D.unpack_records' dict of per-person tensors (None: nobody detected)."""
     B = args.batch
     persons = [0]
+    keep = [None]
     # steady state of a stream of identical jobs (round 6): the shard is walked again next step, so the chunk pipeline stays primed
     # across steps (the next step's first network under this step's last parse + SMPL + all-gather) and the record exchange keeps
     # its capacity (counts inside the one all-gather).  Every step still launches exactly its own number of networks.
@@ -785,14 +840,18 @@ def run_job(args, model, images, lo, rank, world, dev, D, sensors=None):
             out, counts = D.sharded_forward(model, images, lo, with_joints=True, with_verts=bool(args.with_verts), chunk=B, next_images=nxt,
                                             gather_state=gather_state)
             persons[0] = sum(counts)
+            keep[0] = out
         else:
             rec = D.local_records(model, images, lo, chunk=B, with_joints=True, with_verts=bool(args.with_verts), next_images=nxt)
             persons[0] = 0 if rec is None else rec.shape[0]
+            keep[0] = rec
     pre_s, pre_ms = preheat(step, dev, world, cap_s=getattr(args, 'preheat_cap', 10.0)) if getattr(args, 'preheat_cap', 10.0) > 0 else (0.0, [])
     dt, per = timed_steps(step, args.warmup, args.steps, dev, world, sensors)
     pipe = getattr(model, '_pipe', None)
     if pipe is not None:
         pipe['primed'] = None            # (the last step announced a step that will not come: timed_steps has synchronised, nothing is in flight)
+    if last is not None:
+        last['records'] = keep[0] if (world > 1 or keep[0] is None) else D.unpack_records(keep[0], True, bool(args.with_verts))
     timing = {'preheat_s': round(pre_s, 3), 'preheat_step_ms': [round(x, 3) for x in pre_ms],
               'step_ms': step_stats(per.get('gpu', per['host'])), 'step_ms_clock': 'HIP events on the launch stream' if 'gpu' in per else 'host',
               'step_ms_host': step_stats(per['host'])}
@@ -920,10 +979,17 @@ def main():
                 t_lo, t_hi = (mid, t_hi) if kept > 14.0 else (t_lo, mid)
         args.center_thresh = round(mid, 4)
 
-    sensors = GpuSensors(local_rank) if rank == 0 else None
+    sensors = GpuSensors(local_rank) if (rank == 0 and args.full) else None
+    last = {}
     with torch.cuda.stream(stream):
-        dt, persons, timing = run_job(args, model, images, lo, rank, world, dev, D, sensors)
+        dt, persons, timing = run_job(args, model, images, lo, rank, world, dev, D, sensors, last)
     result = headline_result(args, dt, persons, G, n_local, world, dev, variant_table, timing, sensors)
+    if rank == 0 and args.dump_outputs:
+        rec = last['records']
+        if rec is None:
+            rec = D.unpack_records(torch.zeros(0, D.record_width(True, bool(args.with_verts))), True, bool(args.with_verts))
+        dump_outputs(args.dump_outputs, rec)
+    del last
     if rank == 0:
         first = images[:B]
         if args.dump_op_kernels:

@@ -22,7 +22,7 @@ for W in resnet50 bev; do
   # the bench line of the SAME variant table, looking its traffic up in the passes just made
   cp "$OUT/${W}_pmc_FETCH_SIZE_by_kernel.csv" "$REPO/profiles/r02_${W}_pmc_FETCH_SIZE_by_kernel.csv"
   cp "$OUT/${W}_pmc_WRITE_SIZE_by_kernel.csv" "$REPO/profiles/r02_${W}_pmc_WRITE_SIZE_by_kernel.csv"
-  python $REPO/bench.py --tune-file $TUNE $WA --no-f32-companion --no-latency 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_$W.json"
+  python $REPO/bench.py --full --tune-file $TUNE $WA --no-f32-companion --no-latency 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_$W.json"
   python -c "
 import json; r=json.load(open('$OUT/bench_$W.json')); ro=r['roofline']
 print('$W', r['value'], ro['kernel'], ro['bound'], ro['frac'], 'traffic', ro.get('traffic'), 'x', ro.get('traffic_over_algorithmic'))"

@@ -13,7 +13,7 @@ export PYTHONUNBUFFERED=1
 # measuring launches); ${BENCH_ARGS} e.g. "--conv-math f32" or "--workload bev"
 TUNE_ARG=""
 if [ -n "${TUNE_FILE}" ]; then rm -f "$TUNE_FILE"; TUNE_ARG="--tune-file $TUNE_FILE"; fi
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-f32-companion --no-parity --no-end-to-end --no-latency --global-batch 64 $TUNE_ARG ${BENCH_ARGS}"
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-f32-companion --no-parity --no-end-to-end --no-latency --global-batch 64 $TUNE_ARG ${BENCH_ARGS}"
 $BENCH --steps 2 --warmup 1 --no-roofline --dump-op-kernels "$OUT/op_kernels.json" > "$OUT/bench_plain.log" 2>&1
 grep -o '"variant_table": "[^"]*"' "$OUT/bench_plain.log" | head -1
 echo "tune pass exit $? :: $(grep -o '"value": [0-9.]*' "$OUT/bench_plain.log" | head -1)"
@@ -62,11 +62,11 @@ grep '^{' "$OUT/bench_under_rocprof.log" | tail -1 > "$OUT/bench_under_rocprof.j
 grep '^{' "$OUT/bench_under_rocprof_serial.log" | tail -1 > "$OUT/bench_under_rocprof_serial.json"
 # the other workloads: kernel-trace stats only
 if [ -z "${BENCH_ARGS}" ]; then
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_smpl -o stats -- python $REPO/bench.py --workload smpl --no-cpu-baseline > "$OUT/bench_smpl_under_rocprof.log" 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_smpl -o stats -- python $REPO/bench.py --workload smpl --steps 50 --no-cpu-baseline > "$OUT/bench_smpl_under_rocprof.log" 2>&1
   find /tmp/rp_smpl -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_smpl.csv" \;
   rm -f /tmp/romp_tune_bev.json
   python $REPO/bench.py --workload bev --no-cpu-baseline --no-roofline --steps 2 --warmup 1 --tune-file /tmp/romp_tune_bev.json > "$OUT/bench_bev_plain.log" 2>&1
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bev -o stats -- python $REPO/bench.py --workload bev --no-cpu-baseline --steps 5 --warmup 2 --tune-file /tmp/romp_tune_bev.json > "$OUT/bench_bev_under_rocprof.log" 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bev -o stats -- python $REPO/bench.py --full --workload bev --no-cpu-baseline --steps 5 --warmup 2 --tune-file /tmp/romp_tune_bev.json > "$OUT/bench_bev_under_rocprof.log" 2>&1
   find /tmp/rp_bev -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_bev.csv" \;
   grep '^{' "$OUT/bench_bev_under_rocprof.log" | tail -1 > "$OUT/bench_bev_under_rocprof.json"
   head -8 "$OUT/kernel_stats_smpl.csv"; head -12 "$OUT/kernel_stats_bev.csv"
