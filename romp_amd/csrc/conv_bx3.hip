@@ -5,12 +5,10 @@ namespace romp {
 
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 2) void conv_bx3_kernel(ConvParams p) {
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     conv_split_body<3, KS, S, MT, NT, TW, CK>(p);
 }
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 2) void conv_bxd_kernel(ConvParams p) {
-    if (p.dbg & 32) return;
     conv_splitd_body<3, KS, S, MT, NT, TW, CK>(p);
 }
 

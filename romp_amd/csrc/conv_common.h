@@ -45,13 +45,6 @@ struct ConvParams {
                               // clamped a value at +-65504 while splitting it into fp16 pieces (h2_sat): out-of-calibration activations
     int run_len;              // (fused block kernel, strip form) vertically consecutive tiles per run: a work item is a RUN, its tiles hand two
                               // rows of the intermediate on to each other (conv_h2c.h); tiles_y % run_len == 0
-    int dbg;                  // ablation switches, env ROMP_CONV_DEBUG (timing experiments only: outputs are wrong).
-                              // bits: 1 skip global loads / DMA, 2 skip LDS staging writes, 4 skip epilogue, 8 skip MFMA loop,
-                              // 512 (h2r / h2s, correct outputs) the LDS-transposed epilogue instead of the direct one,
-                              // 16 skip a stage barrier (f32 kernel), 32 return at once (launch cost), 64 / 128 (bxd) skip
-                              // only the pixel loads / only the weight DMA; 64 (h2r): every weight fragment load re-reads the first
-                              // tap's 2 KB (same instructions, no weight stream from L2).  scripts/conv_ablate.py, conv_sweep.py and
-                              // DESIGN.md §4 use them.
 };
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -60,14 +53,12 @@ __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cas
 // kernel's first instruction.  hipcc loads a by-value argument where its first use is: the kernels' set-up (early exit, item decode,
 // DMA tables, first stage) then runs 4-8 DEPENDENT s_load / s_waitcnt rounds of ~0.3-0.5 us in front of the first memory request
 // (round 6: profiles/r06s_trace3.txt, r06s_args_ab.txt).  An empty asm that names the fields as SGPR inputs pins their loads here, in
-// one clause under one wait; a field a kernel does not use costs it one more dword of that clause.  -DROMP_NO_ARGS_BATCH: the A/B build.
+// one clause under one wait; a field a kernel does not use costs it one more dword of that clause.
 __device__ __forceinline__ void conv_args_now(const ConvParams& p) {
-#ifndef ROMP_NO_ARGS_BATCH
     asm volatile("" :: "s"(p.in), "s"(p.out), "s"(p.res), "s"(p.wh), "s"(p.scale_h), "s"(p.shift), "s"(p.zero), "s"(p.queue), "s"(p.trace),
                  "s"(p.H), "s"(p.W), "s"(p.Ho), "s"(p.Wo), "s"(p.Cout), "s"(p.cin_valid), "s"(p.cin_pad), "s"(p.cout_pad),
                  "s"(p.in_cs), "s"(p.in_co), "s"(p.in_gs), "s"(p.tiles_x), "s"(p.tiles_y), "s"(p.tiles_total), "s"(p.nslices), "s"(p.ns_total),
-                 "s"(p.n_queues), "s"(p.per_queue), "s"(p.pad_h), "s"(p.pad_w), "s"(p.dbg), "s"(gridDim.x));
-#endif
+                 "s"(p.n_queues), "s"(p.per_queue), "s"(p.pad_h), "s"(p.pad_w), "s"(gridDim.x));
 }
 
 // ---- the H2 activation format -------------------------------------------------------------------------------------
@@ -131,7 +122,7 @@ __device__ __forceinline__ void h2_pack(float4 v, float act_scale, uint2& hi, ui
     // Packed conversions (v_cvt_pk_f16_f32), plain C for the low pieces.  NOT h2_low_pair's asm block here: round 4 measured it in
     // this shared epilogue and the heavily spilling conv_h2_kernel<1,1,4,2,32,32> (784 bytes of scratch per lane) then faulted on
     // the head's 64 -> 142 conv -- in the scalar-store path that never executes the block; the plain form of the same arithmetic
-    // does not (scripts/attic/gpu_r4g.sh isolates it).  The fused kernels keep the asm: they do not spill.
+    // does not (round 4's isolation run: scripts/attic/gpu_r4g.sh at commit 2e43417).  The fused kernels keep the asm: they do not spill.
     typedef float f32x2_p __attribute__((ext_vector_type(2)));
     typedef _Float16 f16x2_p __attribute__((ext_vector_type(2)));
     const f16x2_p h0 = __builtin_convertvector((f32x2_p){x[0], x[1]}, f16x2_p), h1 = __builtin_convertvector((f32x2_p){x[2], x[3]}, f16x2_p);

@@ -72,7 +72,6 @@ __device__ __forceinline__ void mma_stage(const float* sA, const float* sB, cons
 
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvParams p) {
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     using C = ConvCfg<KS, S, MT, NT, TW, CK>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sA = smem;                                  // haloed pixels
@@ -192,13 +191,13 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvParams p) {
         Item tgt = last ? nxt : cur;
         const int c0 = last ? 0 : (ch + 1) * CK;
         if (ch == 0 && tid == 0) j_after = atomicAdd(p.queue + q * QUEUE_STRIDE, 1) + nwg_q;   // item after next
-        if (pf && !(p.dbg & 1)) issue_loads(tgt, c0);
-        if (!(p.dbg & 8)) mma_stage<KS, S, MT, NT, TW, CK>(sA, sB, xoff, woff, acc);
+        if (pf) issue_loads(tgt, c0);
+        mma_stage<KS, S, MT, NT, TW, CK>(sA, sB, xoff, woff, acc);
         if (ch == 0 && tid == 0) sQ[0] = j_after;
-        if (!(p.dbg & 16)) __syncthreads();   // every wave finished reading this stage
-        if (pf && !(p.dbg & 2)) write_lds(last, slot ^ 1);
+        __syncthreads();   // every wave finished reading this stage
+        if (pf) write_lds(last, slot ^ 1);
         if (last) {
-            if (!(p.dbg & 4)) conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
+            conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -231,7 +230,6 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvParams p) {
 // its MFMA phase.  One workgroup-wide barrier per phase.  2 waves/SIMD => up to 256 VGPRs per wave.
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(512) void conv_pp_kernel(ConvParams p) {
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     using C = ConvCfg<KS, S, MT, NT, TW, CK>;
     constexpr int GROUP_FLOATS = C::LDS_BYTES / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];

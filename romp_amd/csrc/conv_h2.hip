@@ -6,7 +6,6 @@ namespace romp {
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 2) void conv_h2_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     conv_split_body<2, KS, S, MT, NT, TW, CK>(p);
 }
 
@@ -14,7 +13,6 @@ __global__ __launch_bounds__(256, 2) void conv_h2_kernel(ConvParams p) {
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 4) void conv_h2o4_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;
     conv_split_body<2, KS, S, MT, NT, TW, CK>(p);
 }
 

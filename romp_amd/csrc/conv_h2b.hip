@@ -51,9 +51,6 @@ __device__ __forceinline__ int unit_of(int c, int w) { return (c >> 2) * 16 + (c
 
 // ConvParams as used here: in = x (H2), res = x, out = y (H2); w3 = conv1's split weights, wh = conv2's; scale = conv1's
 // f16x2 epilogue scale (32), w = conv1's shift (32, as floats), scale_h / shift = conv2's; the geometry fields as for a conv.
-// DBG: timing knock-outs (env ROMP_CONV_DEBUG, wrong outputs): 1 no halo DMA, 2 no hand-over / residual parking, 4 no finish, 8 no MFMA,
-// 64 no fragment reads
-template <int DBG>
 __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
     using X = BCfg;
     using frag = f16x8;
@@ -112,7 +109,6 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
     // outside the image) costs an add, the M0 write and the DMA; an edge tile adds the per-lane test.
     auto is_interior = [&](const Item& it) __attribute__((always_inline)) { return it.ty > 0 && it.ty < p.tiles_y - 1 && it.tx > 0 && it.tx < p.tiles_x - 1; };
     auto fetch_piece = [&](const Item& it, bool valid, bool interior, int ch, int kk) __attribute__((always_inline)) {
-        if (DBG & 1) return;
         if (!valid || (kk == X::NI - 1 && wv != 0)) return;     // (uniform)
         const int iy0 = it.ty * X::TH - 2, ix0 = it.tx * X::TW - 2;
         const int origin = (((it.b * p.H + iy0) * p.W + ix0) * p.in_cs + ch * 16) * 4;    // may be "negative": the sum with d_off is not
@@ -240,7 +236,6 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
         int e_o = 0;
         constexpr int FIN_N = 4 + 4 * 15;
         auto fin_micro = [&](const Item& tl, bool live, int j, int t) __attribute__((always_inline)) {   // output pixel (4 wv + 2 j + li / 16, li % 16), channels 8 g4 + 4 lh .. + 3
-            if (DBG & 4) return;
             auto prep = [&](int g4) __attribute__((always_inline)) {      // (an LDS round trip ahead of its first use: micro-steps 1-3 are empty)
                 e_sc = *reinterpret_cast<const f32x4*>(sS1 + 64 + g4 * 8);
                 e_sh = *reinterpret_cast<const f32x4*>(sS1 + 96 + g4 * 8);
@@ -291,7 +286,6 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
         uint2 pk[4];
         constexpr int PARK_N = 32;
         auto park_micro = [&](int t) __attribute__((always_inline)) {       // r0 r1 r2 | w0 r3 | w1 r4 | ... | w12 r15 | w13 w14 w15
-            if (DBG & 2) return;
             auto rd = [&](int i) __attribute__((always_inline)) {
                 const int j = i / 8, g4 = (i % 8) / 2, pc = i % 2;
                 pk[i % 4] = *reinterpret_cast<const uint2*>(sBuf + (g4 >> 1) * X::STAGE_BYTES + ra2[g4 & 1][pc] + 2 * j * (X::RSU * 16));
@@ -311,7 +305,6 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
         bool h_in = false;
         constexpr int HAND_N = 4 + 4 * 10;
         auto hand_micro = [&](int sl, int t) __attribute__((always_inline)) {
-            if (DBG & 2) return;
             const int my = sl == 2 ? myC : myA + 8 * sl, mx = sl == 2 ? mxC : mxA;
             const bool act = sl == 2 ? actC : true;
             auto prep = [&](int g4) __attribute__((always_inline)) {      // (an LDS round trip ahead of its first use)
@@ -382,19 +375,18 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const int sl = u / 18, ch = (u % 18) / 9, tap = u % 9, v = u % 18;
-                if (u + PF < NU && !((DBG & 64) && u > 2)) read_x(u + PF);
+                if (u + PF < NU) read_x(u + PF);
                 const frag (&x)[2] = xf[u % (PF + 1)];
                 f32x16& aa = acc1[sl];
                 f32x16& ab = acc1[sl];
-                if (!(DBG & 8)) aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][1], x[0], aa, 0, 0, 0);
+                aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][1], x[0], aa, 0, 0, 0);
                 side(sl, v * 3 + 0);
-                if (!(DBG & 8)) ab = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][0], x[1], ab, 0, 0, 0);
+                ab = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][0], x[1], ab, 0, 0, 0);
                 side(sl, v * 3 + 1);
-                if (!(DBG & 8)) aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][0], x[0], aa, 0, 0, 0);
+                aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[ch][tap][0], x[0], aa, 0, 0, 0);
                 side(sl, v * 3 + 2);
             }
             ROMP_TRACE(11);
-            if (DBG & 2) asm volatile("" :: "v"(acc1[0]), "v"(acc1[1]), "v"(acc1[2]));   // (knock-out builds: keep the MFMAs)
 #pragma unroll
             for (int t = 0; t < HAND_N; ++t) hand_micro(2, t); // the last slot's: nothing left to hide it under
             ROMP_TRACE(13);
@@ -436,19 +428,18 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const int j = u / 18, ch = (u % 18) / 9, tap = u % 9, v = u % 18;
-                if (u + PF < NU && !((DBG & 64) && u > 2)) read_x(u + PF);
+                if (u + PF < NU) read_x(u + PF);
                 const frag (&x)[2] = xf[u % (PF + 1)];
                 f32x16& aa = acc2[j];
                 f32x16& ab = acc2[j];
-                if (!(DBG & 8)) aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][1], x[0], aa, 0, 0, 0);
+                aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][1], x[0], aa, 0, 0, 0);
                 side(j, v * 3 + 0);
-                if (!(DBG & 8)) ab = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][0], x[1], ab, 0, 0, 0);
+                ab = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][0], x[1], ab, 0, 0, 0);
                 side(j, v * 3 + 1);
-                if (!(DBG & 8)) aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][0], x[0], aa, 0, 0, 0);
+                aa = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2[ch][tap][0], x[0], aa, 0, 0, 0);
                 side(j, v * 3 + 2);
             }
             ROMP_TRACE(17);
-            if (DBG & 4) asm volatile("" :: "v"(acc2[0]), "v"(acc2[1]));
         }
         // ---- 4. the next halo has landed (and this tile's stores are out), for every wave; m may be overwritten
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -457,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
         itp = it;
         it = itn;
     }
-    if (!(DBG & 4)) {                                          // the last tile's second block
+    {                                                          // the last tile's second block
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             const f32x4 e_sc = *reinterpret_cast<const f32x4*>(sS1 + 64 + g4 * 8);
@@ -503,24 +494,8 @@ int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float
     static bool attr = false;
     static float* zero = nullptr;                              // 256 bytes of zeros: what out-of-image lanes of the halo DMA fetch
     static int num_cu = 256;
-    using KernelFn = void (*)(ConvParams);
-    static KernelFn fn = bblock32_kernel<0>;                    // (always counts the values it clamps: conv_common.h sat_track_pk)
     if (!attr) {                                               // (romp_net_create calls this path's setup outside any stream capture: bblock_init)
-#ifdef ROMP_BBLOCK_KNOCKOUTS                                   // the timing knock-outs: developer builds only (see conv_h2c.h)
-        const char* e = getenv("ROMP_CONV_DEBUG");
-        switch ((e ? atoi(e) : 0) & 127) {
-            case 0: break;
-            case 1: fn = bblock32_kernel<1>; break;
-            case 2: fn = bblock32_kernel<2>; break;
-            case 4: fn = bblock32_kernel<4>; break;
-            case 7: fn = bblock32_kernel<7>; break;
-            case 8: fn = bblock32_kernel<8>; break;
-            case 15: fn = bblock32_kernel<15>; break;
-            case 71: fn = bblock32_kernel<71>; break;
-            default: ROMP_REQUIRE(false, "bblock32: ROMP_CONV_DEBUG & 127 is one of 0 1 2 4 7 8 15 71 here");
-        }
-#endif
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, BCfg::LDS_BYTES));
+        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bblock32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BCfg::LDS_BYTES));
         ROMP_HIP_CHECK(hipMalloc((void**)&zero, 256));
         ROMP_HIP_CHECK(hipMemset(zero, 0, 256));
         int dev = 0;
@@ -567,7 +542,7 @@ int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float
     long grid = num_cu;                                        // one workgroup per CU
     if (grid > p.tiles_total) grid = p.tiles_total;
     if (p.n_queues == 8) grid = grid >= 8 ? (grid / 8) * 8 : 8;
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(256), BCfg::LDS_BYTES, st, p);
+    hipLaunchKernelGGL(bblock32_kernel, dim3((unsigned)grid), dim3(256), BCfg::LDS_BYTES, st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

@@ -69,12 +69,10 @@ struct RCfg {
 
 typedef float f32x4c __attribute__((ext_vector_type(4)));
 
-// DBG: timing knock-outs (env ROMP_CONV_DEBUG, wrong outputs): 1 no halo DMA, 2 no hand-over / parking, 4 no finish, 8 no MFMA --
-// instantiated only in a developer build (-DROMP_BBLOCK_KNOCKOUTS: python -m romp_amd.build with extra_flags; scripts/bblock_bench.py),
-// five more copies of a fully unrolled kernel are most of this file's compile time.  The product kernel (DBG = 0) ALWAYS counts the
-// values it clamps at +-65504 on their way into fp16 pieces (round 6: conv_common.h sat_track_pk, one v_pk_maximum3_f16 per four
-// values; rounds 4-5 had a separate "checked" instantiation that cost 1.7-2 % of the job, profiles/r06_guard_cost*.txt)
-template <int C, int DBG, bool STRIP = false>
+// The kernel ALWAYS counts the values it clamps at +-65504 on their way into fp16 pieces (round 6: conv_common.h sat_track_pk,
+// one v_pk_maximum3_f16 per four values; rounds 4-5 had a separate "checked" instantiation that cost 1.7-2 % of the job,
+// profiles/r06_guard_cost*.txt)
+template <int C, bool STRIP = false>
 __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvParams p) {
     using X = RCfg<C, STRIP>;
     using frag = f16x8;
@@ -166,7 +164,6 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
     }
     auto is_interior = [&](const Item& it) __attribute__((always_inline)) { return it.ty > 0 && it.ty < p.tiles_y - 1 && it.tx > 0 && it.tx < p.tiles_x - 1; };
     auto fetch_piece = [&](const Item& it, bool valid, bool interior, bool first, int kk) __attribute__((always_inline)) {
-        if (DBG & 1) return;
         if (!valid || kk * 4 + wv >= X::NPIECE) return;        // (uniform)
         const int iy0 = it.ty * X::TH - 2, ix0 = it.tx * X::TW - 2;
         const int origin = ((it.b * p.H + iy0) * p.W + ix0) * p.in_cs * 4;     // may be "negative": the sum with d_off is not
@@ -259,7 +256,6 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
         int e_o = 0;
         constexpr int FIN_N = 9;
         auto fin_micro = [&](const Item& tl, bool live, int r, int t) __attribute__((always_inline)) {
-            if (DBG & 4) return;
             switch (t) {
             case 0:
                 e_rh = *reinterpret_cast<const uint2*>(sR + (r * 2 + 0) * 512);
@@ -296,7 +292,6 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
         uint2 pk[4];
         constexpr int PARK_N = 2 * X::THW + 3;
         auto park_micro = [&](int t) __attribute__((always_inline)) {
-            if (DBG & 2) return;
             if (t < 2 * X::THW) pk[t % 4] = *reinterpret_cast<const uint2*>(sBuf + ra + ((t & 1) * X::XPL + (t >> 1) * X::IC) * 16);
             if (t >= 3) *reinterpret_cast<uint2*>(sR + (t - 3) * 512) = pk[(t - 3) % 4];
         };
@@ -306,7 +301,6 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
         unsigned hh[2], hl[2];
         constexpr int HAND_N = 6;
         auto hand_micro = [&](const f32x4c& a, bool inside, bool act, int addr, int t) __attribute__((always_inline)) {
-            if (DBG & 2) return;
             switch (t) {
             case 0: case 1: {
 #pragma unroll
@@ -376,8 +370,7 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
 #pragma unroll
                         for (int e = 0; e < X::NEB; ++e) {
                             const frag (&x)[2] = xf[(u + e) % RING];
-                            if (!(DBG & 8))
-                                accE[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], accE[e], 0, 0, 0);
+                            accE[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], accE[e], 0, 0, 0);
                             const int g = ((tap * X::NKC + kc) * 3 + pr) * X::NEB + e;
                             int lo, hi;
                             share(g, GE, NE, lo, hi);
@@ -405,8 +398,7 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
 #pragma unroll
                             for (int dy = dy_lo; dy <= dy_hi; ++dy) {
                                 const int tap = dy * 3 + dx;
-                                if (!(DBG & 8))
-                                    acc1[Rl - dy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], acc1[Rl - dy], 0, 0, 0);
+                                acc1[Rl - dy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], acc1[Rl - dy], 0, 0, 0);
                                 const int g = (((dx * X::NKC + kc) * 3) + pr) * nv + (dy - dy_lo);
                                 int lo, hi;
                                 share(g, G, HAND_N, lo, hi);
@@ -429,12 +421,6 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
                     }
             }
             ROMP_TRACE(11);
-            if (DBG & 2) {                                     // (knock-out builds: keep every MFMA)
-#pragma unroll
-                for (int r = 0; r < X::MRW; ++r) asm volatile("" :: "v"(acc1[r]));
-#pragma unroll
-                for (int e = 0; e < X::NEB; ++e) asm volatile("" :: "v"(accE[e]));
-            }
 #pragma unroll
             for (int t = 0; t < HAND_N; ++t) hand_micro(acc1[X::MRW - 1], (unsigned)(iy_m0 + X::MRW - 1) < (unsigned)p.Ho, true, hs + (X::MRW - 1) * X::MC * 16, t);
             ROMP_TRACE(13);
@@ -473,11 +459,7 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
 #pragma unroll
                         for (int i = 0; i < 4; ++i) ap[r][pr][i] = 0.f;
                 }
-#ifdef ROMP_BBLOCK_PFP1                                        // (A/B build: one unit ahead at both channel counts, the first form)
-                constexpr int PFP = 1;
-#else
                 constexpr int PFP = C == 64 ? 2 : 1;            // units ahead (64 channels: one wave per SIMD, a unit can be 3 MFMAs = 48 clocks)
-#endif
                 frag xb[PFP + 1][2];
                 auto read_p = [&](int u) __attribute__((always_inline)) {
 #pragma unroll
@@ -703,8 +685,7 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
 #pragma unroll
                         for (int dy = dy_lo; dy <= dy_hi; ++dy) {
                             const int tap = dy * 3 + dx;
-                            if (!(DBG & 8))
-                                acc2[Rl - dy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], acc2[Rl - dy], 0, 0, 0);
+                            acc2[Rl - dy] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2[tap][kc][pr == 0 ? 1 : 0], x[pr == 1 ? 1 : 0], acc2[Rl - dy], 0, 0, 0);
                             const int g = (((dx * X::NKC + kc) * 3) + pr) * nv + (dy - dy_lo);
                             int lo, hi;
                             share(g, G, NS, lo, hi);
@@ -718,24 +699,15 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
                 }
         }
         ROMP_TRACE(17);
-        if (DBG & 4) {
-#pragma unroll
-            for (int r = 0; r < X::THW; ++r) asm volatile("" :: "v"(acc2[r]));
-        }
         // ---- 4. the next halo has landed, for every wave; m may be overwritten.  A COUNTED wait (round 5): the halo pieces go out under
         // the first FR m rows, each output row's store at the end of its row from row 3 on, so exactly MRW2 - max(3, FR - 1) stores are
         // younger than the last piece; a wave's memory operations retire in issue order: "at most that many outstanding" = every piece
         // has landed while the tile's last stores stay in flight across the barrier (vmcnt(0) waited one store round trip per tile
-        // with nothing to compute).  Knock-out builds without the finish have no stores to count on: full drain
+        // with nothing to compute)
         constexpr int FRW = (X::MRW2 + 1) / 2;                  // (= FR of the conv2 loop above)
         constexpr int STORES_AFTER_DMA = X::MRW2 - (FRW - 1 > 3 ? FRW - 1 : 3);
         static_assert(STORES_AFTER_DMA == (C == 64 ? 6 : 3), "the counted wait below");
-#ifdef ROMP_BBLOCK_DRAIN0                                      // (A/B builds: the full drain of rounds 3-4; python -m romp_amd.build with extra_flags)
-        if (true) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
-        if (DBG & 4) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-        else if (C == 64) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+        if (C == 64) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         ROMP_TRACE(15);
@@ -743,7 +715,7 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
         it = itn;
         run = run_n; kr = kr_n;
     }
-    if (!(DBG & 4)) {                                          // the last tile's last output row
+    {                                                          // the last tile's last output row
         const int r = X::THW - 1;
         const uint2 rh = *reinterpret_cast<const uint2*>(sR + (r * 2 + 0) * 512), rl = *reinterpret_cast<const uint2*>(sR + (r * 2 + 1) * 512);
         float ev[4];
@@ -785,21 +757,8 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     static bool attr = false;
     static int num_cu = 256;
     using KernelFn = void (*)(ConvParams);
-    static KernelFn fn = bblockr_kernel<C, 0>;
-    static KernelFn fn_strip = bblockr_kernel<C, 0, true>;
+    const KernelFn fn = bblockr_kernel<C>, fn_strip = bblockr_kernel<C, true>;
     if (!attr) {                                               // (romp_net_create calls this path's set-up outside any stream capture)
-#ifdef ROMP_BBLOCK_KNOCKOUTS
-        const char* e = getenv("ROMP_CONV_DEBUG");
-        switch ((e ? atoi(e) : 0) & 15) {                      // (the other bits belong to other kernels)
-            case 0: break;
-            case 1: fn = bblockr_kernel<C, 1>; break;
-            case 2: fn = bblockr_kernel<C, 2>; break;
-            case 4: fn = bblockr_kernel<C, 4>; break;
-            case 7: fn = bblockr_kernel<C, 7>; break;
-            case 8: fn = bblockr_kernel<C, 8>; break;
-            default: ROMP_REQUIRE(false, "bblock%d: ROMP_CONV_DEBUG & 15 is one of 0 1 2 4 7 8 here", C);
-        }
-#endif
         ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
         ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_strip), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
         int dev = 0;
@@ -866,7 +825,7 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     }
     KernelFn f = fn;
     long items = p.tiles_total;
-    if (L > 1 && fn == bblockr_kernel<C, 0>) {                 // (knock-out builds time the plain kernel)
+    if (L > 1) {
         f = fn_strip;
         p.run_len = L;
         items = p.tiles_total / L;

@@ -6,7 +6,6 @@ namespace romp {
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 2) void conv_h2d_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     conv_splitd_body<2, KS, S, MT, NT, TW, CK>(p);
 }
 
@@ -14,7 +13,6 @@ __global__ __launch_bounds__(256, 2) void conv_h2d_kernel(ConvParams p) {
 template <int KS, int S, int MT, int NT, int TW, int CK>
 __global__ __launch_bounds__(256, 4) void conv_h2do4_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;
     conv_splitd_body<2, KS, S, MT, NT, TW, CK>(p);
 }
 #define ROMP_CONV_VARIANT_H2DO4(KS, S, MT, NT, TW, CK)                                \

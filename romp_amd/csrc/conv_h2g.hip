@@ -66,7 +66,6 @@ struct GStage {                 // wave-uniform description of one stage's sourc
 template <int KS, int P, int NS, int TW, int S, int KSUB>
 __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     using X = GCfg<KS, P, NS, TW, S, KSUB>;
     using C = typename X::C;
     using frag = f16x8;
@@ -100,7 +99,6 @@ __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
         const int w = ((lane & 7) - t) & 7;
         d_rc[k] = (t / TW) | ((t % TW) << 8) | (w << 17);
     }
-    const int cold = (p.dbg & 1) ? 0 : 1;                      // ablation bit 1: every DMA piece reads the zero page (no HBM traffic)
 
     auto make_desc = [&](const Item& it, int st) {
         GStage d;
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
         const int row = rc & 255, col = (rc >> 8) & 255, w = (rc >> 17) & 7;
         const int oy = d.oy0 + row, ox = d.ox0 + col;
         const int iy = oy * S + d.dy, ix = ox * S + d.dx;
-        int ok = (int)(oy < p.Ho) & (int)(d.c0 + sub * 32 + (w >> 1) * 8 < p.cin_valid) & cold;
+        int ok = (int)(oy < p.Ho) & (int)(d.c0 + sub * 32 + (w >> 1) * 8 < p.cin_valid);
         if (KS != 1) ok &= (int)((unsigned)iy < (unsigned)p.H) & (int)((unsigned)ix < (unsigned)p.W);      // (the taps' zero padding)
         const unsigned long long a_in = (unsigned long long)(d.in + ((iy * p.W + ix) * p.in_cs + sub * 32 + w * 4));
         const unsigned long long a = ok ? a_in : (unsigned long long)p.zero;
@@ -194,46 +192,44 @@ __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
         const GStage nd = make_desc(last ? (have_next ? nxt : cur) : cur, last ? (have_next ? 0 : ch) : ch + 1);
         const int nbuf = buf ^ 1;
         ROMP_TRACE(10);
-        if (!(p.dbg & 8)) {
-            const char* sA = sBuf + buf * X::STAGE_BYTES;
-            constexpr int UPT = P / G, NUNIT = NCH * UPT;          // units per chunk, per stage
-            frag xf[PFU + 1][G][2];
-            auto read_x = [&](int u) {
-                const int c = u / UPT, j0 = (u % UPT) * G;
+        const char* sA = sBuf + buf * X::STAGE_BYTES;
+        constexpr int UPT = P / G, NUNIT = NCH * UPT;          // units per chunk, per stage
+        frag xf[PFU + 1][G][2];
+        auto read_x = [&](int u) {
+            const int c = u / UPT, j0 = (u % UPT) * G;
 #pragma unroll
-                for (int g = 0; g < G; ++g)
+            for (int g = 0; g < G; ++g)
 #pragma unroll
-                    for (int pc = 0; pc < 2; ++pc)
-                        xf[u % (PFU + 1)][g][pc] = *reinterpret_cast<const frag*>(sA + (c >> 1) * X::SUB_BYTES + xa[c & 1][pc] + (j0 + g) * 4096);
-            };
-            const uint4* wp = nd.wg + w_lane;                      // chunk c's registers take the next stage's chunk c at its end
+                for (int pc = 0; pc < 2; ++pc)
+                    xf[u % (PFU + 1)][g][pc] = *reinterpret_cast<const frag*>(sA + (c >> 1) * X::SUB_BYTES + xa[c & 1][pc] + (j0 + g) * 4096);
+        };
+        const uint4* wp = nd.wg + w_lane;                      // chunk c's registers take the next stage's chunk c at its end
 #pragma unroll
-            for (int u = 0; u < PFU && u < NUNIT; ++u) read_x(u);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int u = 0; u < PFU && u < NUNIT; ++u) read_x(u);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int u = 0; u < NUNIT; ++u) {
-                const int c = u / UPT, j0 = (u % UPT) * G;
-                if (u + PFU < NUNIT) read_x(u + PFU);
-                const frag (&x)[G][2] = xf[u % (PFU + 1)];
-                // h1w2 + h2w1 + h1w1 (smallest terms first), product-major so that consecutive MFMAs hit different accumulators
+        for (int u = 0; u < NUNIT; ++u) {
+            const int c = u / UPT, j0 = (u % UPT) * G;
+            if (u + PFU < NUNIT) read_x(u + PFU);
+            const frag (&x)[G][2] = xf[u % (PFU + 1)];
+            // h1w2 + h2w1 + h1w1 (smallest terms first), product-major so that consecutive MFMAs hit different accumulators
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][1], x[g][0], acc[j0 + g][0], 0, 0, 0);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][1], x[g][0], acc[j0 + g][0], 0, 0, 0);
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][0], x[g][1], acc[j0 + g][0], 0, 0, 0);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][0], x[g][1], acc[j0 + g][0], 0, 0, 0);
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][0], x[g][0], acc[j0 + g][0], 0, 0, 0);
-                const bool chunk_end = u % UPT == UPT - 1;
-                if (chunk_end) {                                   // chunk done: its registers take the next stage's weights
-                    load_w(wp, c);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[c][0], x[g][0], acc[j0 + g][0], 0, 0, 0);
+            const bool chunk_end = u % UPT == UPT - 1;
+            if (chunk_end) {                                   // chunk done: its registers take the next stage's weights
+                load_w(wp, c);
 #pragma unroll
-                    for (int e = 0; e < X::PPE; ++e) issue_piece(c * X::PPE + e, nd, nbuf);
-                }
-                // the order inside the unit: its look-ahead reads, its MFMAs, the memory issues of a chunk end; units stay in order
-                if (u + PFU < NUNIT) __builtin_amdgcn_sched_group_barrier(0x100, 2 * G, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 3 * G, 0);
-                if (chunk_end) __builtin_amdgcn_sched_group_barrier(0x010, 2 + X::PPE, 0);
-                __builtin_amdgcn_sched_barrier(0);
+                for (int e = 0; e < X::PPE; ++e) issue_piece(c * X::PPE + e, nd, nbuf);
             }
+            // the order inside the unit: its look-ahead reads, its MFMAs, the memory issues of a chunk end; units stay in order
+            if (u + PFU < NUNIT) __builtin_amdgcn_sched_group_barrier(0x100, 2 * G, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 3 * G, 0);
+            if (chunk_end) __builtin_amdgcn_sched_group_barrier(0x010, 2 + X::PPE, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         ROMP_TRACE(11);
         if (last) {
@@ -243,24 +239,22 @@ __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
             // full drain behind the epilogue, same box, all ten ResNet-50 shapes: equal to +-1 %, profiles/r06_h2g_drain_ab.txt --
             // with two workgroups per CU the other one covers the store round trip either way.  Kept: it never waits for a store.)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(p.dbg & 4)) {
-                Item ce = cur;
-                ce.n0 += sl * 32;
-                // (the lane index goes through an opaque move: otherwise hipcc hoists every lane-derived address part of the epilogue
-                // out of the stage loop and holds them in VGPRs across the MFMA stages)
-                int lane_e = lane;
-                asm volatile("" : "+v"(lane_e));
-                const float* sc_e = reinterpret_cast<const float*>(sSb + slot * X::SS_BYTES) + sl * 64;
-                if (p.out_h2 && p.vec_io && (!p.res || p.res_h2) && !(p.dbg & 512)) conv_epilogue_h2direct<KS, S, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
-                else {
-                    char* se = sE;
-                    if (X::EPI_ALIAS) {                            // (a workgroup-uniform branch: every wave meets at this barrier)
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        se = sBuf + buf * X::STAGE_BYTES + wave * EPI_WAVE;
-                    }
-                    conv_epilogue<KS, S, P, 1, TW, 16, PG>(p, ce, acc, sc_e, se, pg, lane_e & 31, lane_e >> 5);
+            Item ce = cur;
+            ce.n0 += sl * 32;
+            // (the lane index goes through an opaque move: otherwise hipcc hoists every lane-derived address part of the epilogue
+            // out of the stage loop and holds them in VGPRs across the MFMA stages)
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));
+            const float* sc_e = reinterpret_cast<const float*>(sSb + slot * X::SS_BYTES) + sl * 64;
+            if (p.out_h2 && p.vec_io && (!p.res || p.res_h2)) conv_epilogue_h2direct<KS, S, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
+            else {
+                char* se = sE;
+                if (X::EPI_ALIAS) {                            // (a workgroup-uniform branch: every wave meets at this barrier)
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    se = sBuf + buf * X::STAGE_BYTES + wave * EPI_WAVE;
                 }
+                conv_epilogue<KS, S, P, 1, TW, 16, PG>(p, ce, acc, sc_e, se, pg, lane_e & 31, lane_e >> 5);
             }
 #pragma unroll
             for (int j = 0; j < P; ++j)

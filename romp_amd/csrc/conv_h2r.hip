@@ -73,7 +73,6 @@ struct RStage {                 // wave-uniform description of one stage's sourc
 template <int P, int NS, int TW, int KSUB = 1>
 __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     using X = RCfg<P, NS, TW, KSUB>;
     using C = typename X::C;
     using frag = f16x8;
@@ -108,14 +107,11 @@ __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
         const int col = cg * 4 + (r16 & 3), w = ((r16 >> 2) - cg) & 3;          // unit w = piece (w & 1) of octet (w >> 1)
         d_rc[k] = row | (col << 8) | ((row < C::HR && col < C::HC) ? 1 << 16 : 0) | (w << 17);
     }
-    const int cold = (p.dbg & 1) ? 0 : 1;                      // ablation bit 1: every DMA piece reads the zero page (no HBM traffic)
-    const int wcold = (p.dbg & 64) ? 0 : 1;                    // ablation bit 64: every weight fragment load re-reads the FIRST tap's 2 KB of the
-                                                               // wave's slice (same instruction stream, L1 hits: no weight traffic from L2)
 
     auto make_desc = [&](const Item& it, int c0) {
         RStage d;
         d.in = p.in + (size_t)it.b * p.H * p.W * p.in_cs + p.in_co + it.g * p.in_gs + c0;
-        d.wg = p.wh + (size_t)it.g * (9 * cin16 * 4 * p.cout_pad) + wcold * (c0 >> 4) * 4 * p.cout_pad + it.n0 + sl * 32;
+        d.wg = p.wh + (size_t)it.g * (9 * cin16 * 4 * p.cout_pad) + (c0 >> 4) * 4 * p.cout_pad + it.n0 + sl * 32;
         d.iy0 = it.ty * C::TH - p.pad_h;
         d.ix0 = it.tx * TW - p.pad_w;
         d.c0 = c0;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
         const int row = rc & 255, col = (rc >> 8) & 255, w = (rc >> 17) & 3;
         const int iy = d.iy0 + row, ix = d.ix0 + col;
         const int ok = ((rc >> 16) & 1) & (int)((unsigned)iy < (unsigned)p.H) & (int)((unsigned)ix < (unsigned)p.W) &
-                       (int)(d.c0 + sub * 16 + (w >> 1) * 8 < p.cin_valid) & cold;
+                       (int)(d.c0 + sub * 16 + (w >> 1) * 8 < p.cin_valid);
         const unsigned long long a_in = (unsigned long long)(d.in + ((iy * p.W + ix) * p.in_cs + sub * 16 + w * 4));
         const unsigned long long a = ok ? a_in : (unsigned long long)p.zero;
         __builtin_amdgcn_global_load_lds((glb_void_r*)a, (lds_void_r*)(sBuf + buf * X::STAGE_BYTES + sub * X::SUB_BYTES + i * 1024), 16, 0, 0);
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
     // weight fragments of one tap: lane (li, lh) holds channel li of the slice, k-half lh
     frag wreg[9][2];
     const unsigned w_lane = (unsigned)(lh * p.cout_pad + li);
-    const unsigned w_tap = (unsigned)(wcold * cin16 * 4 * p.cout_pad), w_pc = (unsigned)(2 * p.cout_pad);   // unit strides of a tap / a piece
+    const unsigned w_tap = (unsigned)(cin16 * 4 * p.cout_pad), w_pc = (unsigned)(2 * p.cout_pad);   // unit strides of a tap / a piece
     // `wp` walks the taps in order (a running per-lane pointer: two strides in SGPRs instead of eighteen hoisted offsets)
     auto load_w = [&](const uint4*& wp, int tap) {
         wreg[tap][0] = __builtin_bit_cast(frag, wp[0]);
@@ -203,78 +199,74 @@ __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
         const RStage nd = make_desc(last ? (have_next ? nxt : cur) : cur, last ? (have_next ? 0 : ch * 16 * KSUB) : (ch + 1) * 16 * KSUB);
         const int nbuf = buf ^ 1;
         ROMP_TRACE(10);
-        if (!(p.dbg & 8)) {
-            const char* sA = sBuf + buf * X::STAGE_BYTES;
-            constexpr int UPT = P / G, NUSUB = 9 * UPT, NUNIT = KSUB * NUSUB;   // units per tap, per sub-stage, per stage
-            frag xf[PFU + 1][G][2];
-            auto read_x = [&](int u) {
-                const int sub = u / NUSUB, tap = (u % NUSUB) / UPT, j0 = (u % UPT) * G;
-                const int dy = tap / 3, dx = tap % 3;
+        const char* sA = sBuf + buf * X::STAGE_BYTES;
+        constexpr int UPT = P / G, NUSUB = 9 * UPT, NUNIT = KSUB * NUSUB;   // units per tap, per sub-stage, per stage
+        frag xf[PFU + 1][G][2];
+        auto read_x = [&](int u) {
+            const int sub = u / NUSUB, tap = (u % NUSUB) / UPT, j0 = (u % UPT) * G;
+            const int dy = tap / 3, dx = tap % 3;
 #pragma unroll
-                for (int g = 0; g < G; ++g)
+            for (int g = 0; g < G; ++g)
 #pragma unroll
-                    for (int pc = 0; pc < 2; ++pc)
-                        xf[u % (PFU + 1)][g][pc] =
-                            *reinterpret_cast<const frag*>(sA + sub * X::SUB_BYTES + xa[dx][pc] + ((j0 + g) * C::RPB + dy) * (X::RSU * 16));
-            };
-            // a tap's registers are re-loaded right after its last MFMA of a sub-stage: with the weights of the NEXT sub-stage (the
-            // same stage's second 16 channels: one chunk = 4 * cout_pad units further on), or of the next stage's first
-            const uint4* wp = (KSUB == 2 ? cwg + wcold * 4 * p.cout_pad : nd.wg) + w_lane;
-            const uint4* wp2 = nd.wg + w_lane;
+                for (int pc = 0; pc < 2; ++pc)
+                    xf[u % (PFU + 1)][g][pc] =
+                        *reinterpret_cast<const frag*>(sA + sub * X::SUB_BYTES + xa[dx][pc] + ((j0 + g) * C::RPB + dy) * (X::RSU * 16));
+        };
+        // a tap's registers are re-loaded right after its last MFMA of a sub-stage: with the weights of the NEXT sub-stage (the
+        // same stage's second 16 channels: one chunk = 4 * cout_pad units further on), or of the next stage's first
+        const uint4* wp = (KSUB == 2 ? cwg + 4 * p.cout_pad : nd.wg) + w_lane;
+        const uint4* wp2 = nd.wg + w_lane;
 #pragma unroll
-            for (int u = 0; u < PFU; ++u) read_x(u);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int u = 0; u < PFU; ++u) read_x(u);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int u = 0; u < NUNIT; ++u) {
-                const int sub = u / NUSUB, tap = (u % NUSUB) / UPT, j0 = (u % UPT) * G;
-                if (u + PFU < NUNIT) read_x(u + PFU);
-                const frag (&x)[G][2] = xf[u % (PFU + 1)];
-                // h1w2 + h2w1 + h1w1 (smallest terms first), product-major so that consecutive MFMAs hit different accumulators
+        for (int u = 0; u < NUNIT; ++u) {
+            const int sub = u / NUSUB, tap = (u % NUSUB) / UPT, j0 = (u % UPT) * G;
+            if (u + PFU < NUNIT) read_x(u + PFU);
+            const frag (&x)[G][2] = xf[u % (PFU + 1)];
+            // h1w2 + h2w1 + h1w1 (smallest terms first), product-major so that consecutive MFMAs hit different accumulators
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][1], x[g][0], acc[j0 + g][0], 0, 0, 0);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][1], x[g][0], acc[j0 + g][0], 0, 0, 0);
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][0], x[g][1], acc[j0 + g][0], 0, 0, 0);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][0], x[g][1], acc[j0 + g][0], 0, 0, 0);
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][0], x[g][0], acc[j0 + g][0], 0, 0, 0);
-                const bool tap_end = u % UPT == UPT - 1;
-                const int te = sub * 9 + tap;                      // tap end number of the stage: DMA piece `te` of the next stage rides along
-                if (tap_end) {                                     // tap done: its registers take the next sub-stage's weights
-                    if (KSUB == 2 && sub == 1) load_w(wp2, tap); else load_w(wp, tap);
-                    if (te < KSUB * X::NI) issue_piece(te, nd, nbuf);
-                }
-                // the order inside the unit: its look-ahead reads, its MFMAs, the memory issues of a tap end; units stay in order
-                if (u + PFU < NUNIT) __builtin_amdgcn_sched_group_barrier(0x100, 2 * G, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 3 * G, 0);
-                if (tap_end) {
-                    if (te < KSUB * X::NI) __builtin_amdgcn_sched_group_barrier(0x010, 3, 0);
-                    else __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+            for (int g = 0; g < G; ++g) acc[j0 + g][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[tap][0], x[g][0], acc[j0 + g][0], 0, 0, 0);
+            const bool tap_end = u % UPT == UPT - 1;
+            const int te = sub * 9 + tap;                      // tap end number of the stage: DMA piece `te` of the next stage rides along
+            if (tap_end) {                                     // tap done: its registers take the next sub-stage's weights
+                if (KSUB == 2 && sub == 1) load_w(wp2, tap); else load_w(wp, tap);
+                if (te < KSUB * X::NI) issue_piece(te, nd, nbuf);
             }
+            // the order inside the unit: its look-ahead reads, its MFMAs, the memory issues of a tap end; units stay in order
+            if (u + PFU < NUNIT) __builtin_amdgcn_sched_group_barrier(0x100, 2 * G, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 3 * G, 0);
+            if (tap_end) {
+                if (te < KSUB * X::NI) __builtin_amdgcn_sched_group_barrier(0x010, 3, 0);
+                else __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
         cwg = nd.wg;
         ROMP_TRACE(11);
         if (last) {
             if (have_next) issue_ss(nxt, slot ^ 1);
-            if (!(p.dbg & 4)) {
-                Item ce = cur;
-                ce.n0 += sl * 32;
-                // (the lane index goes through an opaque move: otherwise hipcc hoists every lane-derived address part of the epilogue
-                // out of the stage loop and holds them in VGPRs across the MFMA stages)
-                int lane_e = lane;
-                asm volatile("" : "+v"(lane_e));
-                const float* sc_e = reinterpret_cast<const float*>(sSb + slot * X::SS_BYTES) + sl * 64;
-                // H2 out (+ H2 residual): the direct epilogue (conv_common.h; ROMP_CONV_DEBUG=512 keeps the LDS-transposed one: A/B runs)
-                if (p.out_h2 && p.vec_io && (!p.res || p.res_h2) && !(p.dbg & 512)) conv_epilogue_h2direct<3, 1, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
-                else {
-                    char* se = sE;
-                    if (X::EPI_ALIAS) {                            // (a workgroup-uniform branch: every wave meets at this barrier)
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        se = sBuf + buf * X::STAGE_BYTES + wave * EPI_WAVE;
-                    }
-                    conv_epilogue<3, 1, P, 1, TW, 16, PG>(p, ce, acc, sc_e, se, pg, lane_e & 31, lane_e >> 5);
+            Item ce = cur;
+            ce.n0 += sl * 32;
+            // (the lane index goes through an opaque move: otherwise hipcc hoists every lane-derived address part of the epilogue
+            // out of the stage loop and holds them in VGPRs across the MFMA stages)
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));
+            const float* sc_e = reinterpret_cast<const float*>(sSb + slot * X::SS_BYTES) + sl * 64;
+            // H2 out (+ H2 residual): the direct epilogue (conv_common.h)
+            if (p.out_h2 && p.vec_io && (!p.res || p.res_h2)) conv_epilogue_h2direct<3, 1, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
+            else {
+                char* se = sE;
+                if (X::EPI_ALIAS) {                            // (a workgroup-uniform branch: every wave meets at this barrier)
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    se = sBuf + buf * X::STAGE_BYTES + wave * EPI_WAVE;
                 }
+                conv_epilogue<3, 1, P, 1, TW, 16, PG>(p, ce, acc, sc_e, se, pg, lane_e & 31, lane_e >> 5);
             }
 #pragma unroll
             for (int j = 0; j < P; ++j)

@@ -57,7 +57,6 @@ struct SStage {                 // wave-uniform description of one stage's sourc
 template <int P, int NS, int TW>
 __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
     conv_args_now(p);
-    if (p.dbg & 32) return;                            // ablation: launch cost only
     using X = SCfg<P, NS, TW>;
     using C = typename X::C;
     using frag = f16x8;
@@ -95,7 +94,6 @@ __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
         const int hr = 2 * prow + (plane >> 1), hc = 2 * col + (plane & 1);
         d_rc[k] = hr | (hc << 8) | ((plane < 4 && hr < C::HR && hc < C::HC) ? 1 << 16 : 0) | (w << 17);
     }
-    const int cold = (p.dbg & 1) ? 0 : 1;                      // ablation bit 1: every DMA piece reads the zero page (no HBM traffic)
 
     auto make_desc = [&](const Item& it, int c0) {
         SStage d;
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
         const int row = rc & 255, col = (rc >> 8) & 255, w = (rc >> 17) & 3;
         const int iy = d.iy0 + row, ix = d.ix0 + col;
         const int ok = ((rc >> 16) & 1) & (int)((unsigned)iy < (unsigned)p.H) & (int)((unsigned)ix < (unsigned)p.W) &
-                       (int)(d.c0 + (w >> 1) * 8 < p.cin_valid) & cold;
+                       (int)(d.c0 + (w >> 1) * 8 < p.cin_valid);
         const unsigned long long a_in = (unsigned long long)(d.in + ((iy * p.W + ix) * p.in_cs + w * 4));
         const unsigned long long a = ok ? a_in : (unsigned long long)p.zero;
         __builtin_amdgcn_global_load_lds((glb_void_s*)a, (lds_void_s*)(sBuf + buf * X::STAGE_BYTES + i * 1024), 16, 0, 0);
@@ -189,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
         if (!active) {                                             // the pixel mover of an NS = 3 workgroup
 #pragma unroll
             for (int k = 0; k < X::NI; ++k) issue_piece(k, nd, nbuf);
-        } else if (!(p.dbg & 8)) {
+        } else {
             const char* sA = sBuf + buf * X::STAGE_BYTES;
             constexpr int UPT = P / G, NUNIT = 9 * UPT;            // units per tap, per stage
             frag xf[PFU + 1][G][2];
@@ -240,13 +238,13 @@ __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
         ROMP_TRACE(11);
         if (last) {
             if (have_next) issue_ss(nxt, slot ^ 1);
-            if (active && !(p.dbg & 4)) {
+            if (active) {
                 Item ce = cur;
                 ce.n0 += sl * 32;
                 int lane_e = lane;
                 asm volatile("" : "+v"(lane_e));               // (see conv_h2r.hip: keeps the epilogue's address parts out of the stage loop)
                 const float* sc_e = reinterpret_cast<const float*>(sSb + slot * X::SS_BYTES) + sl * 64;
-                if (p.out_h2 && p.vec_io && (!p.res || p.res_h2) && !(p.dbg & 512)) conv_epilogue_h2direct<3, 2, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
+                if (p.out_h2 && p.vec_io && (!p.res || p.res_h2)) conv_epilogue_h2direct<3, 2, P, TW, PG>(p, ce, acc, sc_e, pg, lane_e & 31, lane_e >> 5);
                 else conv_epilogue<3, 2, P, 1, TW, 16, PG>(p, ce, acc, sc_e, sE, pg, lane_e & 31, lane_e >> 5);
             }
 #pragma unroll

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void seam1x1_kernel(ConvParams p) {
         // ---- the next m (x0) has landed (see the header): everything older than the operations issued after the DMAs has completed.
         // Barrier: every wave's share of it is there, t may be overwritten
         static_assert(X::after_dma(0) == 52 && X::after_dma(1) == 20, "the counted waits below");
-        // (DRAIN = 1: the full drain of round 3 -- its own instantiation, chosen by ROMP_CONV_DEBUG=1024, so that a GPU test can compare
+        // (DRAIN = 1: the full drain of round 3 -- its own instantiation, chosen by env ROMP_SEAM_FULL_DRAIN=1, so that a GPU test can compare
         // the counted waits bit for bit against it; a RUN-TIME switch here made hipcc spill the DS = 1 tile loop)
         if (DRAIN) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         else if (DS) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
@@ -310,7 +310,6 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
     p.scale_h = opb.scale_h2; p.shift = opb.shift;
     p.act_scale = ldexpf(1.f, opa.act_shift);
     p.sat = conv_sat_counter();
-    { const char* e = getenv("ROMP_CONV_DEBUG"); p.dbg = e ? (atoi(e) & 1024) : 0; }      // 1024: the full-drain builds (tests)
     {
         const unsigned long long bytes = ((unsigned long long)B * opa.H * opa.W * opa.in_cstride - opa.in_coff) * 4ull;
         ROMP_REQUIRE(bytes < 0x80000000ull, "seam1x1: input tensor of %llu bytes: beyond the 31-bit offsets of the DMA", bytes);
@@ -331,7 +330,8 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
     p.tiles_total = (int)(((long)B * opa.H * opa.W) / XCfg::N);
     long grid = num_cu;
     if (grid > p.tiles_total) grid = p.tiles_total;
-    if (p.dbg & 1024) {
+    const char* drain = getenv("ROMP_SEAM_FULL_DRAIN");       // the full-drain builds: the tests' reference for the counted waits
+    if (drain && atoi(drain)) {
         if (opd) hipLaunchKernelGGL((seam1x1_kernel<1, 1>), dim3((unsigned)grid), dim3(256), XCfg::lds_bytes(1), st, p);
         else hipLaunchKernelGGL((seam1x1_kernel<0, 1>), dim3((unsigned)grid), dim3(256), XCfg::lds_bytes(0), st, p);
     } else if (opd) hipLaunchKernelGGL(seam1x1_kernel<1>, dim3((unsigned)grid), dim3(256), XCfg::lds_bytes(1), st, p);

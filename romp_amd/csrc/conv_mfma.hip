@@ -208,7 +208,6 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
     p.tiles_x = p.tiles_y = p.tiles_total = 1;
     p.nslices = p.ns_total = p.n_queues = p.per_queue = 1;
     p.queue = nullptr;
-    { const char* e = getenv("ROMP_CONV_DEBUG"); p.dbg = e ? atoi(e) : 0; }
     p.trace = nullptr;
     p.vec_io = (op.Cout == op.cout_pad && (op.Cout & 3) == 0 && (op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0 && (op.out_gstride & 3) == 0 &&
                 (!res || ((op.res_cstride & 3) == 0 && (op.res_coff & 3) == 0 && (op.res_gstride & 3) == 0))) ? 1 : 0;

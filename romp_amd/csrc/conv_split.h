@@ -348,26 +348,24 @@ __device__ __forceinline__ void conv_split_body(const ConvParams& p) {
         Item tgt = last ? nxt : cur;
         const int c0 = last ? 0 : (ch + 1) * CK;
         if (ch == 0 && tid == 0) j_after = atomicAdd(p.queue + q * QUEUE_STRIDE, 1) + nwg_q;
-        if (pf && !(p.dbg & 1)) issue_loads(tgt, c0);
+        if (pf) issue_loads(tgt, c0);
         ROMP_TRACE(10);                                // stage start: next loads issued
-        if (p.dbg & 256) __builtin_amdgcn_s_setprio(2);        // experiment: the wave in its MFMA block wins issue arbitration
-        if (!(p.dbg & 8)) mma_stage_split<NP, KS, S, MT, NT, TW, CK>(sA, sB, xoff, woff, acc);
-        if (p.dbg & 256) __builtin_amdgcn_s_setprio(0);
+        mma_stage_split<NP, KS, S, MT, NT, TW, CK>(sA, sB, xoff, woff, acc);
         ROMP_TRACE(11);                                // MFMA block done
         if (ch == 0 && tid == 0) sQ[0] = j_after;
         __syncthreads();
         ROMP_TRACE(12);                                // barrier: all waves done reading
         if (X::EPI_ALIAS && last) {                    // epilogue first: it stages through the (now dead) pixel / weight regions
-            if (!(p.dbg & 4)) conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
+            conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
             ROMP_TRACE(14);
             if (!have_next) break;
             __syncthreads();                           // every wave is done with its staging tile
         }
-        if (pf && !(p.dbg & 2)) write_lds(last, slot ^ 1);
+        if (pf) write_lds(last, slot ^ 1);
         ROMP_TRACE(13);                                // next stage written to LDS
         if (last) {
             if (!X::EPI_ALIAS) {
-                if (!(p.dbg & 4)) conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
+                conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
                 ROMP_TRACE(14);                        // epilogue issued
             }
             if (NP == 2 && !p.in_h2) { sat_report(p.sat, sat_in); sat_in = 0.f; }
@@ -546,36 +544,32 @@ __device__ __forceinline__ void conv_splitd_body(const ConvParams& p) {
         const int c0B = last_row ? (last_ch ? 0 : (ch + 1) * CK) : ch * CK;
         const int rowB = last_row ? 0 : row + 1;
         if (ch == 0 && row == 0 && tid == 0) j_after = atomicAdd(p.queue + q * QUEUE_STRIDE, 1) + nwg_q;
-        if (pfB && !(p.dbg & (1 | 128))) issue_B(tgtB, c0B, rowB, bbuf ^ 1);
+        if (pfB) issue_B(tgtB, c0B, rowB, bbuf ^ 1);
         const bool pfA = last_row && pfB;                          // next chunk's pixels: loaded under the last tap row
-        if (pfA && !(p.dbg & (1 | 64))) issue_A(tgtB, c0B);
+        if (pfA) issue_A(tgtB, c0B);
         __builtin_amdgcn_sched_barrier(0);               // keep every DMA / load issue ABOVE the MFMA block (hipcc sank 3 of the 5 DMAs below it)
         ROMP_TRACE(10);
-        if (p.dbg & 256) __builtin_amdgcn_s_setprio(2);
-        if (!(p.dbg & 8)) {
-            const char* sBc = sB + bbuf * (X::SUB_UNITS * 16);
+        const char* sBc = sB + bbuf * (X::SUB_UNITS * 16);
 #pragma unroll
-            for (int dx = 0; dx < C::KW; ++dx)
+        for (int dx = 0; dx < C::KW; ++dx)
 #pragma unroll
-                for (int k16 = 0; k16 < X::K16; ++k16) {
-                    frag xf[MT][NP], wf[NT][NP];
+            for (int k16 = 0; k16 < X::K16; ++k16) {
+                frag xf[MT][NP], wf[NT][NP];
 #pragma unroll
-                    for (int m = 0; m < MT; ++m)
+                for (int m = 0; m < MT; ++m)
 #pragma unroll
-                        for (int pc = 0; pc < NP; ++pc)
-                            xf[m][pc] = *reinterpret_cast<const frag*>(sA + xoff[m] + row * X::ROWB + dx * X::PSB + frag_off<NP, CK>(k16, pc));
+                    for (int pc = 0; pc < NP; ++pc)
+                        xf[m][pc] = *reinterpret_cast<const frag*>(sA + xoff[m] + row * X::ROWB + dx * X::PSB + frag_off<NP, CK>(k16, pc));
 #pragma unroll
-                    for (int n = 0; n < NT; ++n)
+                for (int n = 0; n < NT; ++n)
 #pragma unroll
-                        for (int pc = 0; pc < NP; ++pc)
-                            wf[n][pc] = *reinterpret_cast<const frag*>(sBc + woff + ((((dx * NP + pc) * X::K16 + k16) * 2) * C::NW + n * 32) * 16);
+                    for (int pc = 0; pc < NP; ++pc)
+                        wf[n][pc] = *reinterpret_cast<const frag*>(sBc + woff + ((((dx * NP + pc) * X::K16 + k16) * 2) * C::NW + n * 32) * 16);
 #pragma unroll
-                    for (int m = 0; m < MT; ++m)
+                for (int m = 0; m < MT; ++m)
 #pragma unroll
-                        for (int n = 0; n < NT; ++n) acc[m][n] = Piece<NP>::mma(wf[n], xf[m], acc[m][n]);
-                }
-        }
-        if (p.dbg & 256) __builtin_amdgcn_s_setprio(0);
+                    for (int n = 0; n < NT; ++n) acc[m][n] = Piece<NP>::mma(wf[n], xf[m], acc[m][n]);
+            }
         ROMP_TRACE(11);
         if (ch == 0 && row == 0 && tid == 0) sQ[2 + par] = j_after;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's LDS-DMA has landed (and ra is in)
@@ -587,16 +581,16 @@ __device__ __forceinline__ void conv_splitd_body(const ConvParams& p) {
             if (X::EPI_ALIAS_DMA && last_ch) {                     // epilogue first: it stages through the pixel region and the consumed row buffer
                 char* se = wave < X::EPI_IN_A ? sA + wave * EPI_WAVE
                                               : sB + (bbuf ^ 1) * (X::SUB_UNITS * 16) + (wave - X::EPI_IN_A) * EPI_WAVE;
-                if (!(p.dbg & 4)) conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, se, wave, li, lh);
+                conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, se, wave, li, lh);
                 ROMP_TRACE(14);
                 if (!have_next) break;
                 __syncthreads();                                   // every wave is done with its staging tile
             }
-            if (pfA && !(p.dbg & 2)) write_A(last_ch, slot ^ 1);
+            if (pfA) write_A(last_ch, slot ^ 1);
             ROMP_TRACE(13);
             if (last_ch) {
                 if (!X::EPI_ALIAS_DMA) {
-                    if (!(p.dbg & 4)) conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
+                    conv_epilogue<KS, S, MT, NT, TW, CK>(p, cur, acc, sS + slot * 2 * C::NW, sE, wave, li, lh);
                     ROMP_TRACE(14);
                 }
                 if (NP == 2 && !p.in_h2) { sat_report(p.sat, sat_in); sat_in = 0.f; }

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void smpl_skin_kernel(const float* __restrict_
                                                          const float* __restrict__ Amat, const float* __restrict__ vt,
                                                          const float* __restrict__ sd, const float* __restrict__ pd,
                                                          const float* __restrict__ lbsw, const float* __restrict__ reg, int N, int groups,
-                                                         float* __restrict__ verts, float* __restrict__ jpart, int dbg) {
+                                                         float* __restrict__ verts, float* __restrict__ jpart) {
     __shared__ __attribute__((aligned(16))) float s_u[U_FLOATS];          // pose features, then blend partials, then the vertex tile
     __shared__ __attribute__((aligned(16))) float s_A[5 * 256 * 4];       // PB x 24 x 12 (+ staging slack); later: the regressor tile [NREG][RS]
     __shared__ float s_beta[PB][NB];
@@ -241,8 +241,8 @@ __global__ __launch_bounds__(256) void smpl_skin_kernel(const float* __restrict_
     for (int p = 0; p < PB / 2; ++p) po[p][0] = po[p][1] = po[p][2] = f2{0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-        if (c + 1 < NCH && !(dbg & 2)) pd_load(d[(c + 1) & 1], pdv, k0 + (c + 1) * KC);
-        if (!(dbg & 8)) pd_blend(po, d[c & 1], s_pf, k0 + c * KC);
+        if (c + 1 < NCH) pd_load(d[(c + 1) & 1], pdv, k0 + (c + 1) * KC);
+        pd_blend(po, d[c & 1], s_pf, k0 + c * KC);
     }
     // per-vertex constants of the finishing phase and the regressor tile: in flight across the exchange of the partials
     const float t0 = vt[v * 3 + 0], t1 = vt[v * 3 + 1], t2 = vt[v * 3 + 2];
@@ -295,7 +295,6 @@ __global__ __launch_bounds__(256) void smpl_skin_kernel(const float* __restrict_
 #pragma unroll
         for (int e = 0; e < 6; ++e) T[e] = f2{0.f, 0.f};
         const float* Ap = s_A + p * NJ * 12;
-        if (!(dbg & 4))
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {              // T = W @ A   (smpl.py:179)
             const float4 a0v = *reinterpret_cast<const float4*>(Ap + j * 12);
@@ -326,7 +325,7 @@ __global__ __launch_bounds__(256) void smpl_skin_kernel(const float* __restrict_
     __syncthreads();
     // joints 45..70 (extra9 then h36m17, smpl.py:26-29): this tile's 64 terms of  regressor @ vertices; one thread per
     // (person, regressor pair), 16-byte LDS reads along the vertices
-    if (tid < PB * RPAIRS && !(dbg & 1)) {
+    if (tid < PB * RPAIRS) {
         const int p = tid % PB, rp = tid / PB;
         const float* sv = s_u + p * SVS;
         const float* sr = s_A + rp * 2 * RS;
@@ -418,7 +417,6 @@ struct smpl_ctx {
     int nb = 10;
     int cap = 0;
     Parents par;
-    int dbg = 0;                   // ROMP_SMPL_DBG: phase knock-outs for timing experiments (results are wrong when set)
     int* sched = nullptr;          // [n_levels, start[MAXLV + 1], order[NJ], parent[NJ]] for the pose kernel
     float* jpart = nullptr;        // (cap, NT, NREG, 3) per-tile joint partial sums
     float *vt = nullptr, *sd = nullptr, *pd = nullptr, *lbsw = nullptr, *reg = nullptr, *Jt = nullptr, *Js = nullptr;
@@ -457,7 +455,6 @@ int smpl_ctx_create(smpl_ctx** out, const float* v_template, const float* shaped
     hipStream_t st = (hipStream_t)stream;
     smpl_ctx* c = new smpl_ctx();
     c->nb = n_betas;
-    if (const char* e = getenv("ROMP_SMPL_DBG")) c->dbg = atoi(e);
     for (int j = 0; j < NJ; ++j) {
         c->par.p[j] = (int)parents_host[j];
         if (j > 0 && (c->par.p[j] < 0 || c->par.p[j] >= j)) {
@@ -540,10 +537,10 @@ int smpl_forward(smpl_ctx* c, const float* betas, int n_betas, const float* thet
     const dim3 grid(8 * ((NT + 7) / 8) * groups);
     if (c->nb == 10)
         hipLaunchKernelGGL(smpl_skin_kernel<10>, grid, dim3(256), 0, st, betas, c->pose_feat, c->Amat, c->vt, c->sd, c->pd,
-                           c->lbsw, c->reg, N, groups, verts, c->jpart, c->dbg);
+                           c->lbsw, c->reg, N, groups, verts, c->jpart);
     else
         hipLaunchKernelGGL(smpl_skin_kernel<11>, grid, dim3(256), 0, st, betas, c->pose_feat, c->Amat, c->vt, c->sd, c->pd,
-                           c->lbsw, c->reg, N, groups, verts, c->jpart, c->dbg);
+                           c->lbsw, c->reg, N, groups, verts, c->jpart);
     ROMP_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(smpl_joints_kernel, dim3(N), dim3(256), 0, st, verts, c->jpart, c->pick, root_align, joints, c->root);
     ROMP_HIP_CHECK(hipGetLastError());

@@ -85,6 +85,6 @@ if __name__ == '__main__':
     check = os.environ.get('SWEEP_CHECK', '0') == '1'
     cases = sum(CASES.values(), []) if which == 'all' else sum((CASES[k] for k in which.split(',')), [])
     for case in cases:
-        print('case', case, 'B=%d' % B, 'dbg=%s' % os.environ.get('ROMP_CONV_DEBUG', '0'), flush=True)
+        print('case', case, 'B=%d' % B, flush=True)
         for name, v, us, tf, err in sorted(run_case(case, B, filt, check), key=lambda r: r[2]):
             print('  %-40s v%-3d %8.1f us %7.1f TF  %s' % (name, v, us, tf, err), flush=True)

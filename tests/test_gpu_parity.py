@@ -1431,7 +1431,7 @@ def test_seam1x1_counted_waits_vs_full_drain(dev, ds, monkeypatch):
     """the seam kernel ends a tile on a COUNTED wait (vmcnt(52) / vmcnt(20)) that lets stores and the next residual stay in
     flight across the barrier; if the compiled loop ever issued fewer memory operations behind the DMA than the count, the barrier
     would release before the next m tile has landed -- a silent LDS race.  scripts/check_counted_waits.py counts the compiled
-    instructions (CPU test); here the same programs run with the full-drain instantiation (ROMP_CONV_DEBUG=1024: vmcnt(0), round 3's
+    instructions (CPU test); here the same programs run with the full-drain instantiation (ROMP_SEAM_FULL_DRAIN=1: vmcnt(0), round 3's
     form) and must give bit-identical tensors, eight tiles deep per workgroup."""
     import ctypes as C
     from romp_amd import lib as L
@@ -1463,8 +1463,8 @@ def test_seam1x1_counted_waits_vs_full_drain(dev, ds, monkeypatch):
     try:
         xd = img.to(dev).contiguous()
         dummy = torch.empty(16, device=dev)
-        for dbg in ('0', '1024', '0'):
-            monkeypatch.setenv('ROMP_CONV_DEBUG', dbg)
+        for drain in ('0', '1', '0'):
+            monkeypatch.setenv('ROMP_SEAM_FULL_DRAIN', drain)
             for rep in range(3):
                 L.check(lib.romp_net_forward(h, L.ptr(xd), B, L.ptr(dummy), L.ptr(dummy), L.stream_ptr(dev)))
                 for act, name in ((at, 't'), (au, 'u')):
@@ -1474,7 +1474,7 @@ def test_seam1x1_counted_waits_vs_full_drain(dev, ds, monkeypatch):
                     torch.cuda.synchronize()
                     bits = out.view(torch.int32).cpu()
                     if name in got:
-                        assert torch.equal(bits, got[name]), 'seam ds=%s, ROMP_CONV_DEBUG=%s, pass %d: tensor %s differs from the first run' % (ds, dbg, rep, name)
+                        assert torch.equal(bits, got[name]), 'seam ds=%s, ROMP_SEAM_FULL_DRAIN=%s, pass %d: tensor %s differs from the first run' % (ds, drain, rep, name)
                     else:
                         got[name] = bits
     finally:
