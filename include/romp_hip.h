@@ -373,6 +373,25 @@ int  romp_bev_postprocess(const float* joints /* (N,71,3) */, const float* cam /
                           int B, const float* pad_info, float nms_thresh, float relative_scale_thresh,
                           float* pj2d, float* pj2d_org, float* cam_trans, int32_t* keep, void* stream);
 
+/* BEV's long-image "crowd" mode (bev/main.py:184-258, bev/split2process.py).  A wide H x W frame is padded left and right with
+ * pad_length zero columns (padding_image_overlap; the padded frame is virtual) and cut into K crops, crops_host[K][4] =
+ * left, right, top, bottom in padded-frame coordinates (get_image_split_plan); every crop must lie inside the padded frame.
+ * romp_preprocess_crops: img_preprocess of every crop, each with its own centred square pad, in one launch (up to 64 crops;
+ * more take one launch per 64): BGR uint8 (H,W,3) -> RGB float32 (K,S,S,3), bit-identical to romp_preprocess of the cut crop;
+ * pad_info_host[K][6] (may be NULL) receives each crop's top,bottom,left,right,h,w. */
+int  romp_preprocess_crops(const unsigned char* bgr_u8, int H, int W, int pad_length, int K, const int32_t* crops_host,
+                           float* out_rgb_f32, int out_size, float* pad_info_host, void* stream);
+/* The merge of the per-crop detections: rows offsets[c]..offsets[c+1]-1 (offsets: K+1 int32, device, 0 .. N) are crop c's people
+ * with joints (N,71,3), crop-space cam (N,3) and center_confs (N).  Boundary exclusion, per-crop projection, conf-based duplicate
+ * suppression and outlier removal (scale 1), the conversion to full-frame cameras, then the full-frame projection, conf-based
+ * suppression and outlier removal (scale 0.5) over all survivors.  -> cam_full (N,3), cam_trans (N,3), pj2d_org (N,71,2) in
+ * frame pixels, keep[row] = 1 for the survivors.  N <= capacity (the rows the outputs and the workspace hold); workspace:
+ * 4 * capacity + 4 int32.  Nothing synchronises. */
+int  romp_bev_crowd_merge(const float* joints, const float* cam, const float* center_confs, const int32_t* offsets, int N,
+                          int capacity, int K, const int32_t* crops_host, int H, int W, int pad_length, double nms_thresh,
+                          float relative_scale_thresh, float* cam_full, float* cam_trans, float* pj2d_org, int32_t* keep,
+                          int32_t* workspace, void* stream);
+
 /* ---- Sim3DR mesh renderer -------------------------------------------------
  * Replaces the Cython/C++ extension `Sim3DR_Cython` (simple_romp/vis_human/sim3drender/lib/rasterize.pyx,
  * rasterize_kernel.cpp) and the per-vertex lighting of renderer.py:64-110.  Bit-identical images.

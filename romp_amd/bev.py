@@ -9,7 +9,11 @@ Network (HRNet-32 + BEV head), 3-D center parsing, per-person regression, SMPL-A
 perspective projection, projection-based duplicate suppression and outlier removal
 (bev/post_parser.py:68-136,167-222) all run in libromp_hip.so.  Video mode (``-t``): ByteTrack-3D association on the host
 (tracker.py) + OneEuro filters on the device (temporal.py); ``--render_mesh``: the Sim3DR rasteriser (renderer.py).
-Not built: the long-image "crowd" sliding window (bev/main.py:184-258, CPU orchestration of repeated single forwards).
+Crowd mode (``--crowd``, bev/main.py:184-258, bev/split2process.py): a frame with W / H >= 2 is cut into overlapping crops that
+go through ONE batched pre-processing launch (csrc/crowd.hip), the network in chunks of ``max_batch``, one SMPL-A / SMIL call
+and a device merge (boundary exclusion, per-crop and full-frame suppression / outlier removal).  The reference turns crowd mode
+on by default; here it stays off unless asked for.  One deviation: where the reference raises because a crop before a crop
+with people has no detections, an empty crop here simply contributes nobody.
 """
 import argparse
 import ctypes as C
@@ -35,13 +39,17 @@ def bev_settings(input_args=sys.argv[1:]):
     p.add_argument('--model_id', type=int, default=2)
     p.add_argument('-i', '--input', type=str, default=None)
     p.add_argument('-o', '--save_path', type=str, default=osp.join(osp.expanduser('~'), 'BEV_results'))
-    p.add_argument('--crowd', action='store_true', help='long-image sliding window (not built)')
+    p.add_argument('--crowd', action='store_true',
+                   help='process a frame with width / height >= 2 as overlapping crops (sliding window) and merge their people; '
+                        '[romp_amd] off by default, the reference defaults it to on')
     p.add_argument('--GPU', type=int, default=0)
     p.add_argument('--overlap_ratio', type=float, default=0.8)
     p.add_argument('--center_thresh', type=float, default=0.1)
     p.add_argument('--nms_thresh', type=float, default=20)
     p.add_argument('--relative_scale_thresh', type=float, default=1.6)
     p.add_argument('--show_largest', action='store_true')
+    p.add_argument('--show_patch_results', action='store_true',
+                   help='[romp_amd] accepted for compatibility, not supported: no per-crop renderings are written')
     p.add_argument('--calc_smpl', action='store_false')
     p.add_argument('--render_mesh', action='store_true',
                    help='[romp_amd] off by default (the reference defaults to on with a bird view that needs its pyrender/cv2 overlays)')
@@ -59,7 +67,41 @@ def bev_settings(input_args=sys.argv[1:]):
     args = p.parse_args(input_args)
     if not torch.cuda.is_available():
         args.GPU = -1
+    if args.crowd:                                                          # bev/main.py:79-83
+        args.center_thresh, args.nms_thresh, _, args.overlap_ratio = LONG_CONF[args.model_id]
+        args.relative_scale_thresh = LONG_CONF[MODEL_ID][2]                 # (indexed with the module-global model id, as there)
     return args
+
+
+MODEL_ID = 2                                                                # bev/main.py:24-25
+LONG_CONF = {1: [0.12, 20, 1.5, 0.46], 2: [0.08, 20, 1.6, 0.8]}           # center_thresh, nms_thresh, relative_scale_thresh, overlap
+
+
+def crowd_pad_length(h, overlap_ratio):
+    """padding_image_overlap (bev/split2process.py:6-21): zero columns added on each side of the frame."""
+    return int(h * overlap_ratio)
+
+
+def crowd_pad_info(h, w):
+    """padding_image_overlap's image_pad_info, on the unpadded size: the square-padding convention of the full frame."""
+    top = (w - h) // 2
+    return [float(top), float(w - top), 0., float(w), float(h), float(w)]
+
+
+def crowd_split_plan(h, w_pad, overlap_ratio):
+    """get_image_split_plan (bev/split2process.py:23-37) on the padded width -> (K,4) int32 left, right, top, bottom.  The last
+    crop's left is w_pad - h, its right the one left over from the previous step (so it is narrower than h)."""
+    slide_time = int(np.ceil((w_pad / h - 1) / (1 - overlap_ratio))) + 1
+    move_step = (1 - overlap_ratio) * h
+    boxes = []
+    for ind in range(slide_time):
+        if ind == slide_time - 1:
+            left = w_pad - h
+        else:
+            left = move_step * ind
+            right = left + h
+        boxes.append([left, right, 0, h])
+    return np.array(boxes).astype(np.int32)
 
 
 TAN_FOV = float(np.tan(np.radians(60 / 2.)))
@@ -191,15 +233,13 @@ class BEV(nn.Module):
         self.settings = settings
         if settings.GPU == -1:
             raise L.RompHipError('romp_amd.bev needs a HIP device; there is no CPU fallback')
-        if settings.crowd:
-            raise NotImplementedError('crowd mode (long-image sliding window, bev/main.py:184-258) is host orchestration outside the MI355X hot path')
         self.tdevice = determine_device(settings.GPU)
         if state_dict is None:
             state_dict = torch.load(settings.model_path, map_location='cpu')
         self.model = BEVv1(state_dict, self.tdevice, center_thresh=settings.center_thresh,
                            max_batch=getattr(settings, 'max_batch', 32),
                            bf16x3=getattr(settings, 'conv_math', 'f16x2'))
-        if settings.calc_smpl:
+        if settings.calc_smpl or settings.crowd:                           # (crowd mode merges on the meshes' joints)
             self.smpl_parser = SMPLA_parser(smpla_model if smpla_model is not None else settings.smpl_path,
                                             smil_model if smil_model is not None else settings.smil_path).to(self.tdevice)
         self.result_keys = ['smpl_thetas', 'smpl_betas', 'cam', 'cam_trans', 'params_pred', 'center_confs', 'pred_batch_ids']
@@ -289,8 +329,74 @@ class BEV(nn.Module):
             out[k] = v
         return out
 
+    @torch.no_grad()
+    def process_long_image(self, full_image, show_patch_results=False):
+        """bev/main.py:184-258: BGR uint8 HxWx3 frame -> dict of device tensors (the merged people of all crops) or None.
+        show_patch_results is not supported (ignored)."""
+        lib = L.load()
+        dev = self.tdevice
+        H, W = full_image.shape[:2]
+        pad_length = crowd_pad_length(H, self.settings.overlap_ratio)
+        crops = np.ascontiguousarray(crowd_split_plan(H, W + 2 * pad_length, self.settings.overlap_ratio), np.int32)
+        K = crops.shape[0]
+        crops_c = crops.ctypes.data_as(C.POINTER(C.c_int32))
+        img = torch.from_numpy(np.ascontiguousarray(full_image)).to(dev)
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
+        inputs = torch.empty(K, 512, 512, 3, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            L.check(lib.romp_preprocess_crops(L.ptr(img), H, W, pad_length, K, crops_c, L.ptr(inputs), 512, None,
+                                              L.stream_ptr(dev)))
+        parts = []
+        step = self.model.net.max_batch
+        for s in range(0, K, step):                                         # the network in chunks of max_batch crops
+            out = self.model(inputs[s:s + step])
+            if out is not None:
+                part = {k: out[k] for k in self.result_keys}
+                part['pred_batch_ids'] = out['pred_batch_ids'] + s          # -> crop index
+                parts.append(part)
+        if not parts:
+            return None
+        res = {k: torch.cat([p[k] for p in parts]) if len(parts) > 1 else parts[0][k] for k in self.result_keys}
+        crop_ids = res.pop('pred_batch_ids')
+        N = crop_ids.shape[0]
+        verts, joints, face = self.smpl_parser(res['smpl_betas'], res['smpl_thetas'])
+        offsets = torch.zeros(K + 1, dtype=torch.int32, device=dev)
+        offsets[1:] = torch.cumsum(torch.bincount(crop_ids, minlength=K), 0).int()
+        f32 = dict(device=dev, dtype=torch.float32)
+        cam, trans, pjo = torch.empty(N, 3, **f32), torch.empty(N, 3, **f32), torch.empty(N, 71, 2, **f32)
+        keep = torch.empty(N, dtype=torch.int32, device=dev)
+        ws = torch.empty(4 * N + 4, dtype=torch.int32, device=dev)
+        joints, crop_cam, confs = joints.contiguous(), res['cam'].contiguous(), res['center_confs'].contiguous()
+        with torch.cuda.device(dev):
+            L.check(lib.romp_bev_crowd_merge(L.ptr(joints), L.ptr(crop_cam), L.ptr(confs), L.ptr(offsets), N, N, K, crops_c, H, W,
+                                             pad_length, float(self.settings.nms_thresh),
+                                             float(self.settings.relative_scale_thresh), L.ptr(cam), L.ptr(trans), L.ptr(pjo),
+                                             L.ptr(keep), L.ptr(ws), L.stream_ptr(dev)))
+        rows = torch.nonzero(keep).squeeze(1)                               # the one host synchronisation of the merge
+        n = rows.shape[0]
+        if n == 0:
+            return None
+        out = {k: res[k][rows] for k in ('smpl_thetas', 'smpl_betas')}
+        out.update({'cam': cam[rows], 'cam_trans': trans[rows], 'params_pred': res['params_pred'][rows],
+                    'center_confs': res['center_confs'][rows],
+                    'pred_batch_ids': torch.zeros(n, dtype=torch.int64, device=dev),   # every crop was a B = 1 forward there
+                    'verts': verts[rows], 'joints': joints[rows], 'pj2d_org': pjo[rows], 'smpl_face': face})
+        return out
+
     def forward(self, image, signal_ID=0, **kwargs):
-        """bev/main.py:139-181 (normal images): BGR uint8 HxWx3 -> dict of numpy arrays or None."""
+        """bev/main.py:139-181: BGR uint8 HxWx3 -> dict of numpy arrays or None.  With --crowd, a frame with W / H >= 2 takes
+        process_long_image (no tracking / filtering, no --show_largest there, as in the reference)."""
+        if self.settings.crowd and image.shape[1] / image.shape[0] >= 2:
+            res = self.process_long_image(image)
+            if res is None:
+                return None
+            if self.settings.render_mesh:
+                H, W = image.shape[:2]
+                res['verts_camed_org'] = self._verts_camed_org(res['verts'], res['cam_trans'], crowd_pad_info(H, W))
+                from .vis import rendering_romp_bev_results
+                cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': getattr(self.settings, 'renderer', 'sim3dr')}
+                res = rendering_romp_bev_results(self.renderer, res, image, cfgs)
+            return convert_tensor2numpy(res)
         input_image, image_pad_info = img_preprocess_device(image, self.tdevice)
         if not (self.settings.temporal_optimize or self.settings.render_mesh):
             res = self.forward_batch(input_image, image_pad_info.reshape(1, 6))

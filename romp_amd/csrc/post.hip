@@ -14,61 +14,18 @@
 //    One workgroup per image; persons of an image are contiguous rows.  Output: projections and a
 //    keep mask (the caller drops the rows).
 #include "common.h"
+#include "cv_cubic.h"
 
 namespace romp {
 
-// cv::resize(INTER_CUBIC) tables for one destination coordinate, exactly as OpenCV builds them (resize.cpp: the sampling
-// position in double, the cubic weights in float with A = -0.75, then 11-bit fixed point with round-half-even).  `fp contract(off)`
-// keeps hipcc from fusing a*b+c into an FMA, which OpenCV's scalar code does not do.
-__device__ __forceinline__ void cv_cubic_tab(int d, int src, int dst, int& s0, int (&coef)[4]) {
-#pragma clang fp contract(off)
-    const double scale = 1.0 / ((double)dst / (double)src);
-    const double fd = ((double)d + 0.5) * scale - 0.5;
-    const float f = (float)fd;
-    const int fl = (int)floorf(f);
-    const float x = f - (float)fl;
-    const float A = -0.75f;
-    const float xp = x + 1.f, xm = 1.f - x;
-    float c[4];
-    c[0] = ((A * xp - 5.f * A) * xp + 8.f * A) * xp - 4.f * A;
-    c[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-    c[2] = ((A + 2.f) * xm - (A + 3.f)) * xm * xm + 1.f;
-    c[3] = 1.f - c[0] - c[1] - c[2];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) coef[k] = min(max((int)rintf(c[k] * 2048.f), -32768), 32767);
-    s0 = fl - 1;
-}
-
-// One thread per output pixel of one frame (blockIdx.y): the 4x4 taps of the PADDED square image (zero padding around the
-// frame, replicated border of the padded image), horizontal pass to int32, vertical pass, (v + 2^21) >> 22, saturate.
+// One thread per output pixel of one frame (blockIdx.y): the OpenCV cubic resize of the PADDED square image (cv_cubic.h).
 __global__ void preprocess_kernel(const unsigned char* __restrict__ src_all, int H, int W, int side, int top, int left,
                                   float* __restrict__ dst_all, int S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= S * S) return;
     const unsigned char* src = src_all + (size_t)blockIdx.y * H * W * 3;
     float* dst = dst_all + (size_t)blockIdx.y * S * S * 3;
-    const int ox = i % S, oy = i / S;
-    int sx, sy, ca[4], cb[4];
-    cv_cubic_tab(ox, side, S, sx, ca);
-    cv_cubic_tab(oy, side, S, sy, cb);
-    int acc[3] = {0, 0, 0};
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int py = min(max(sy + a, 0), side - 1) - top;             // replicated border of the PADDED image
-        int row[3] = {0, 0, 0};
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int px = min(max(sx + b, 0), side - 1) - left;
-            // branch-free (taps in the zero padding read pixel 0 with weight 0): all 48 byte loads of a thread in flight
-            const bool ok = (unsigned)py < (unsigned)H && (unsigned)px < (unsigned)W;
-            const unsigned char* p = src + (ok ? ((size_t)py * W + px) * 3 : 0);
-            const int wgt = ok ? ca[b] : 0;
-            row[0] += wgt * (int)p[2]; row[1] += wgt * (int)p[1]; row[2] += wgt * (int)p[0];       // BGR -> RGB
-        }
-        acc[0] += row[0] * cb[a]; acc[1] += row[1] * cb[a]; acc[2] += row[2] * cb[a];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = (float)min(max((acc[c] + (1 << 21)) >> 22, 0), 255);
+    cv_cubic_pixel(src, (size_t)W * 3, 0, 0, 0, H, 0, W, side, top, left, i % S, i / S, S, dst + (size_t)i * 3);
 }
 
 constexpr int PJ = 71, PMAX = 64;
