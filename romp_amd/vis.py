@@ -1,11 +1,12 @@
 """Mesh visualisation glue -- mirror of ``simple_romp/vis_human/main.py`` for the Sim3DR renderer
-(``setup_renderer`` :11-21, ``rendering_romp_bev_results`` :23-113, item 'mesh') and of
-``vis_utils.mesh_color_left2right`` (:147-153).  The rasterization runs on the device (renderer.py here);
-pyrender / open3d back-ends, bird / side views and the cv2 overlays are not part of the MI355X path."""
+(``setup_renderer`` :11-21, ``rendering_romp_bev_results`` :23-113, items 'mesh', 'mesh_bird_view',
+'mesh_side_view') and of ``vis_utils.mesh_color_left2right`` (:147-153).  The view transform and the
+rasterization run on the device (renderer.py here); pyrender / open3d back-ends and the cv2 overlays
+(pj2d, j3d, center_conf, tracking) are not part of the MI355X path."""
 import numpy as np
 import torch
 
-from .renderer import Sim3DR
+from .renderer import Sim3DR, view_weak_perspective
 
 # vis_utils.py:128-141 -- the palette persons are coloured with, left to right in the image
 color_table_default = np.array([
@@ -29,9 +30,17 @@ def mesh_color_left2right(trans, color_table=None):
     return np.array([table[i % len(table)] for i in inds])
 
 
+# show_items drawn on the device, in the order rendering_romp_bev_results appends their panels
+DEVICE_ITEMS = ('mesh', 'mesh_bird_view', 'mesh_side_view')
+
+
 def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1):
-    """main.py:23-113 for renderer 'sim3dr', item 'mesh': persons painted far to near onto the frame;
-    `outputs['rendered_image']` = [frame | rendering] side by side."""
+    """main.py:23-113 for renderer 'sim3dr': persons painted far to near.  `outputs['rendered_image']` =
+    [frame | mesh | bird view | side view], the panels of `rendering_cfgs['items']` in this fixed order whatever
+    order the items are listed in.  'mesh': onto the frame.  The views: the meshes in camera space
+    (verts + cam_trans, z negated), rotated and fitted by view_weak_perspective, onto a white h x h canvas.
+    As in the reference, the side view is fitted to the frame's (h, w), not to the h x h canvas it is drawn on:
+    for a frame wider than high its centre lies at x = w / 2, right of the canvas centre (kept, not fixed)."""
     triangles = outputs['smpl_face'].cpu().numpy().astype(np.int32)
     cam_trans = outputs['cam_trans']
     if rendering_cfgs['mesh_color'] == 'identity':
@@ -40,14 +49,28 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
         mesh_colors = np.array([[.9, .9, .8] for _ in range(len(cam_trans))])
     else:
         raise ValueError(rendering_cfgs['mesh_color'])
-    unsupported = [it for it in rendering_cfgs['items'] if it != 'mesh']
+    items = rendering_cfgs['items']
+    unsupported = [it for it in items if it not in DEVICE_ITEMS]
     if unsupported:
-        raise NotImplementedError('show_items %s need OpenCV drawing / extra views; only "mesh" is on the device path' % unsupported)
+        raise NotImplementedError('show_items %s need OpenCV drawing (pj2d / j3d / center_conf / tracking), which is not on the '
+                                  'device path' % unsupported)
+    h, w = image.shape[:2]
     result_image = [image]
     depth_order = torch.sort(cam_trans[:, 2].cpu(), descending=True).indices
-    vertices = outputs['verts_camed_org'][depth_order.to(outputs['verts_camed_org'].device)].clone()
-    vertices[:, :, 2] = vertices[:, :, 2] * -1
-    rendered = renderer(vertices, triangles, np.ascontiguousarray(image), mesh_colors=mesh_colors[depth_order.numpy()])
-    result_image.append(rendered)
+    colors = mesh_colors[depth_order.numpy()]
+    if 'mesh' in items:
+        vertices = outputs['verts_camed_org'][depth_order.to(outputs['verts_camed_org'].device)].clone()
+        vertices[:, :, 2] = vertices[:, :, 2] * -1
+        result_image.append(renderer(vertices, triangles, np.ascontiguousarray(image), mesh_colors=colors))
+    views = [(it, rx, ry, shape) for it, rx, ry, shape in (('mesh_bird_view', -90, 0, (h, h)), ('mesh_side_view', 0, -90, (h, w)))
+             if it in items]
+    if views:
+        verts = outputs['verts']
+        verts_tran = (verts + cam_trans.to(verts.device).unsqueeze(1))[depth_order.to(verts.device)].float()
+        verts_tran[:, :, 2] = verts_tran[:, :, 2] * -1
+        background = torch.full((h, h, 3), 255, dtype=torch.uint8, device=verts_tran.device)
+        for _, rx, ry, shape in views:
+            view = view_weak_perspective(verts_tran, rx, ry, shape, expand_ratio=1.2)[0] if len(verts_tran) else verts_tran
+            result_image.append(renderer(view, triangles, background, mesh_colors=colors))
     outputs['rendered_image'] = np.concatenate(result_image, 1)
     return outputs
