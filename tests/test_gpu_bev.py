@@ -3,6 +3,10 @@ oracle (oracle/bev_oracle.py) and the reference-generated fixtures (bev_b1.npz, 
 
 Tolerances: 3-D center / camera maps 1e-4 max-abs (float32 conv stack + Conv1d K=7680 + two 3-D
 convs); detections exact as a set on fixture inputs; params_pred 2e-4; SMPL-A meshes 1e-4.
+
+These are whole-network and API tests.  Each kernel of csrc/bev.hip ALONE (conv3d, bev_maps, bev_pack, the parse's edge cases, the
+regression on crafted cams) is in tests/test_gpu_bev_kernels.py, against oracle/bev_kernels_ref.py, whose restatements
+tests/test_bev_kernel_refs.py pins on the CPU.
 """
 import ctypes as C
 import os

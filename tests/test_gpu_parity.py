@@ -183,6 +183,9 @@ CONV_CASES = [
     (256, 1024, 1, 1, 32, True, True), (1024, 256, 1, 1, 32, True, False), (512, 1024, 1, 2, 64, False, False),
     (512, 2048, 1, 1, 16, True, True), (2048, 512, 1, 1, 16, True, False), (1024, 2048, 1, 2, 32, False, False),
     (96, 64, 1, 1, 32, True, False), (64, 64, 1, 2, 64, True, False),          # 32-channel stages; a small strided 1x1
+    # the BEV head's 2-D layers (bev/model.py:154-175): the merged 32 -> 256 first conv of det_head | param_head and the 16-channel
+    # bv_pre layers (its two-group conv2 and the channel-slice 128 -> 4 output conv are in tests/test_gpu_bev_kernels.py)
+    (32, 256, 3, 1, 128, True, False), (32, 16, 1, 1, 128, True, False), (16, 16, 3, 1, 128, True, False), (16, 16, 1, 1, 128, True, False),
 ]
 
 
