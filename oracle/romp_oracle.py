@@ -465,9 +465,10 @@ def batch_rodrigues(rv, dtype=np.float32):
     return (np.eye(3, dtype=dtype)[None] + s * K + (1 - c) * (K @ K)).astype(dtype)
 
 
-def smpl_forward(model, betas, poses, root_align=False, dtype=np.float32):
+def smpl_forward(model, betas, poses, root_align=False, dtype=np.float32, parents=None):
     """SMPL.forward + lbs + VertexJointSelector (smpl.py:24-35, 62-108, 111-188, 236-290).
-    model: dict as loaded from the .pth; betas (N,10|11), poses (N,72).
+    model: dict as loaded from the .pth; betas (N,10|11), poses (N,72); parents: another kinematic tree than the
+    model's own (24 entries, parents[j] < j; entry 0 is ignored), the reference's loop :269-275 over it.
     Returns verts (N,6890,3), joints (N,71,3), J_transformed (N,24,3)."""
     g = lambda k: np.asarray(model[k].numpy() if torch.is_tensor(model[k]) else model[k])
     betas, poses = np.asarray(betas, dtype), np.asarray(poses, dtype)
@@ -475,7 +476,7 @@ def smpl_forward(model, betas, poses, root_align=False, dtype=np.float32):
     sdirs = g('smpla_shapedirs' if betas.shape[1] == 11 else 'shapedirs').astype(dtype)
     v_t, pdirs = g('v_template').astype(dtype), g('posedirs').astype(dtype)
     Jreg, W = g('J_regressor').astype(dtype), g('weights').astype(dtype)
-    parents = g('kintree_table').astype(np.int64)
+    parents = (g('kintree_table') if parents is None else np.asarray(parents)).astype(np.int64)
     v_shaped = v_t[None] + np.einsum('bl,mkl->bmk', betas, sdirs)                  # :153
     J = np.einsum('bik,ji->bjk', v_shaped, Jreg)                                    # :156
     R = batch_rodrigues(poses.reshape(-1, 3), dtype).reshape(N, 24, 3, 3)           # :163

@@ -424,7 +424,8 @@ struct smpl_ctx {
     float *pose_feat = nullptr, *Amat = nullptr, *root = nullptr;
 };
 
-static int smpl_reserve(smpl_ctx* c, int N) {
+// `st`: the stream of the call that will use the buffers; the clear is ordered on it, ahead of that call's pose kernel
+static int smpl_reserve(smpl_ctx* c, int N, hipStream_t st) {
     if (N <= c->cap) return ROMP_OK;
     if (c->pose_feat) hipFree(c->pose_feat);
     if (c->Amat) hipFree(c->Amat);
@@ -437,8 +438,8 @@ static int smpl_reserve(smpl_ctx* c, int N) {
     ROMP_HIP_CHECK(hipMalloc((void**)&c->Amat, cap * NJ * 12 * 4));
     ROMP_HIP_CHECK(hipMalloc((void**)&c->root, cap * 3 * 4));
     ROMP_HIP_CHECK(hipMalloc((void**)&c->jpart, cap * NT * NREG * 3 * 4));
-    ROMP_HIP_CHECK(hipMemset(c->pose_feat, 0, cap * NPF * 4));   // rows of a partial last group stay finite
-    ROMP_HIP_CHECK(hipMemset(c->Amat, 0, cap * NJ * 12 * 4));
+    ROMP_HIP_CHECK(hipMemsetAsync(c->pose_feat, 0, cap * NPF * 4, st));   // rows of a partial last group stay finite
+    ROMP_HIP_CHECK(hipMemsetAsync(c->Amat, 0, cap * NJ * 12 * 4, st));
     c->cap = (int)cap;
     return ROMP_OK;
 }
@@ -514,8 +515,13 @@ int smpl_ctx_create(smpl_ctx** out, const float* v_template, const float* shaped
         smpl_ctx_destroy(c);
         return ROMP_EHIP;
     }
-    int rc = smpl_reserve(c, max_persons > 0 ? max_persons : 64);
+    int rc = smpl_reserve(c, max_persons > 0 ? max_persons : 64, st);
     if (rc) { smpl_ctx_destroy(c); return rc; }
+    if (hipStreamSynchronize(st) != hipSuccess) {        // the first forward may come on another stream
+        set_error("smpl_ctx_create: clearing the staging buffers failed");
+        smpl_ctx_destroy(c);
+        return ROMP_EHIP;
+    }
     *out = c;
     return ROMP_OK;
 }
@@ -525,9 +531,9 @@ int smpl_forward(smpl_ctx* c, const float* betas, int n_betas, const float* thet
     ROMP_REQUIRE(c && betas && thetas && verts && joints && N >= 0, "smpl_forward: bad arguments");
     ROMP_REQUIRE(n_betas == c->nb, "smpl_forward: n_betas %d but context was built with %d", n_betas, c->nb);
     if (N == 0) return ROMP_OK;
-    int rc = smpl_reserve(c, N);
-    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    int rc = smpl_reserve(c, N, st);
+    if (rc) return rc;
     if (c->nb == 10)
         hipLaunchKernelGGL(smpl_pose_kernel<10>, dim3(N), dim3(64), 0, st, betas, thetas, c->Jt, c->Js, c->sched, c->pose_feat, c->Amat, joints);
     else
