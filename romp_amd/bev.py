@@ -65,9 +65,14 @@ def bev_settings(input_args=sys.argv[1:]):
     p.add_argument('--max_batch', type=int, default=32)
     p.add_argument('--conv_math', type=str, default='f16x2', choices=['f32', 'bf16x3', 'f16x2', 'all'],
                    help='[romp_amd] f32 MFMA only, or also the f32-accurate split-precision kernels (f16x2: 2 fp16 pieces; bf16x3; chosen by autotune)')
+    p.add_argument('--dense_maps', action='store_true',
+                   help='[romp_amd] also return per-pixel maps of the mesh panel (person_map, part_map, depth_map) and per-person '
+                        'verts_visible / person_pixels, computed on the device (vis.dense_maps)')
     args = p.parse_args(input_args)
     if not torch.cuda.is_available():
         args.GPU = -1
+    if args.dense_maps:
+        args.calc_smpl = True
     if args.crowd:                                                          # bev/main.py:79-83
         args.center_thresh, args.nms_thresh, _, args.overlap_ratio = LONG_CONF[args.model_id]
         args.relative_scale_thresh = LONG_CONF[MODEL_ID][2]                 # (indexed with the module-global model id, as there)
@@ -253,6 +258,9 @@ class BEV(nn.Module):
             from .vis import setup_renderer
             self.renderer = setup_renderer(name=getattr(settings, 'renderer', 'sim3dr'), device=self.tdevice)
             self.visualize_items = getattr(settings, 'show_items', 'mesh').split(',')
+        elif getattr(settings, 'dense_maps', False):
+            from .vis import setup_renderer
+            self.renderer = setup_renderer(device=self.tdevice)
 
     def temporal_optimization(self, outputs, signal_ID, image_scale=128, depth_scale=30):
         """bev/main.py:260-287: ByteTrack-3D association on the host (tracker.py), OneEuro filters on the device (temporal.py).
@@ -391,15 +399,10 @@ class BEV(nn.Module):
             res = self.process_long_image(image)
             if res is None:
                 return None
-            if self.settings.render_mesh:
-                H, W = image.shape[:2]
-                res['verts_camed_org'] = self._verts_camed_org(res['verts'], res['cam_trans'], crowd_pad_info(H, W))
-                from .vis import rendering_romp_bev_results
-                cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': getattr(self.settings, 'renderer', 'sim3dr')}
-                res = rendering_romp_bev_results(self.renderer, res, image, cfgs)
-            return convert_tensor2numpy(res)
+            H, W = image.shape[:2]
+            return convert_tensor2numpy(self._visualize(res, image, crowd_pad_info(H, W)))
         input_image, image_pad_info = img_preprocess_device(image, self.tdevice)
-        if not (self.settings.temporal_optimize or self.settings.render_mesh):
+        if not (self.settings.temporal_optimize or self.settings.render_mesh or getattr(self.settings, 'dense_maps', False)):
             res = self.forward_batch(input_image, image_pad_info.reshape(1, 6))
             return None if res is None else convert_tensor2numpy(res)
         out = self.model(input_image)
@@ -415,12 +418,26 @@ class BEV(nn.Module):
             verts, joints, face = self.smpl_parser(res['smpl_betas'], res['smpl_thetas'])
             res.update({'verts': verts, 'joints': joints, 'smpl_face': face})
             res = self._postprocess(res, 1, image_pad_info.reshape(1, 6))
-            if self.settings.render_mesh:                                                   # bev/main.py:147-150
-                res['verts_camed_org'] = self._verts_camed_org(res['verts'], res['cam_trans'], image_pad_info)
-                from .vis import rendering_romp_bev_results
-                cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': getattr(self.settings, 'renderer', 'sim3dr')}
-                res = rendering_romp_bev_results(self.renderer, res, image, cfgs)
+            res = self._visualize(res, image, image_pad_info)
         return convert_tensor2numpy(res)
+
+    def _visualize(self, res, image, pad_info):
+        """--render_mesh (bev/main.py:147-150) and --dense_maps on the meshes of one frame; with both, the 'mesh' panel's raster
+        pass serves the maps too.  The part labels are the adult model's (SMPL-A) table for every person, infants included:
+        SMIL shares SMPL's topology, so one table indexes every mesh; a per-person SMIL table is not kept."""
+        dense = getattr(self.settings, 'dense_maps', False)
+        if not (self.settings.render_mesh or dense):
+            return res
+        from .vis import dense_maps, mesh_panel_keys, rendering_romp_bev_results
+        res['verts_camed_org'] = self._verts_camed_org(res['verts'], res['cam_trans'], pad_info)
+        keys = None
+        if self.settings.render_mesh:
+            keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
+            cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': getattr(self.settings, 'renderer', 'sim3dr')}
+            res = rendering_romp_bev_results(self.renderer, res, image, cfgs, keys=keys)
+        if dense:
+            res = dense_maps(self.renderer, res, image.shape, self.smpl_parser.smpl_model.part_labels, keys=keys)
+        return res
 
     def _verts_camed_org(self, verts, cam_trans, pad_info):
         lib = L.load()

@@ -26,6 +26,7 @@
 // steps, bbox centre 0.5*(min+max), scale 1/(expand_ratio*max|xy/(w/2,h/2)|); three launches, no host sync.
 #include "common.h"
 #include "../../include/romp_hip_views.h"
+#include "../../include/romp_hip_maps.h"
 
 #pragma clang fp contract(off)
 
@@ -228,6 +229,73 @@ __global__ void sim3dr_resolve_kernel(const float* __restrict__ v, const int32_t
     }
 }
 
+// Dense maps (romp_hip_maps.h): what the resolve pass decides per pixel, kept instead of painted.  One thread per pixel,
+// the key decoded and the weights recomputed exactly as in sim3dr_resolve_kernel; background values where key == 0, so
+// every byte of every non-null output is written.  C floats per pixel of attr_map are one store of C dwords: a wave
+// writes 64 * C * 4 contiguous bytes, as it does 768 for bary_map.  person_pixels: one integer atomicAdd per distinct mesh
+// of a wave (neighbouring pixels mostly share the mesh), so no thread leaves before the count.  vert_visible: racing
+// stores of the same byte.  No float atomics: the outputs do not depend on the order of execution.
+template <int C>
+__global__ __launch_bounds__(256) void sim3dr_maps_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri,
+                                                          const unsigned long long* __restrict__ keys, int nver, int mbits,
+                                                          int h, int w, const int32_t* __restrict__ mesh_ids,
+                                                          const float* __restrict__ attrs, float attr_bg,
+                                                          const uint8_t* __restrict__ vert_labels, int32_t* __restrict__ person_map,
+                                                          int32_t* __restrict__ tri_map, float* __restrict__ bary_map,
+                                                          float* __restrict__ attr_map, uint8_t* __restrict__ label_map,
+                                                          uint8_t* __restrict__ vert_visible, int32_t* __restrict__ person_pixels) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = i < (size_t)h * w;
+    const unsigned long long key = inside ? keys[i] : 0ull;
+    int mesh = -1, t = -1;
+    if (key != 0ull) {                                                    // no fragment: orderable(d > -1e8) is never 0
+        const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
+        t = (int)(tmask - (key & tmask));
+        mesh = mbits ? (int)(key >> (64 - mbits)) : 0;
+    }
+    if (inside) {
+        float w0 = 0.f, w1 = 0.f, w2 = 0.f;
+        int a = 0, b = 0, cc = 0;
+        if (t >= 0) {
+            const float* vm = v + (size_t)mesh * nver * 3;
+            const int x = (int)(i % w), y = (int)(i / w);
+            a = tri[3 * t]; b = tri[3 * t + 1]; cc = tri[3 * t + 2];
+            point_weight((float)x, (float)y, vm[3 * a], vm[3 * a + 1], vm[3 * b], vm[3 * b + 1], vm[3 * cc], vm[3 * cc + 1], w0, w1, w2);
+        }
+        if (person_map) person_map[i] = t < 0 ? -1 : (mesh_ids ? mesh_ids[mesh] : mesh);
+        if (tri_map) tri_map[i] = t;
+        if (bary_map) { bary_map[3 * i] = w0; bary_map[3 * i + 1] = w1; bary_map[3 * i + 2] = w2; }
+        if (attr_map) {
+            const float* am = attrs + (size_t)max(mesh, 0) * nver * C;
+            float val[C];
+            for (int k = 0; k < C; ++k)
+                val[k] = t < 0 ? attr_bg : (w0 * am[C * a + k] + w1 * am[C * b + k]) + w2 * am[C * cc + k];
+            for (int k = 0; k < C; ++k) attr_map[C * i + k] = val[k];
+        }
+        if (label_map) {
+            int corner = a;                                               // the greatest weight, the lowest corner on ties
+            float best = w0;
+            if (w1 > best) { best = w1; corner = b; }
+            if (w2 > best) corner = cc;
+            label_map[i] = t < 0 ? (uint8_t)255 : vert_labels[corner];
+        }
+        if (vert_visible && t >= 0) {
+            uint8_t* vis = vert_visible + (size_t)mesh * nver;
+            vis[a] = 1; vis[b] = 1; vis[cc] = 1;
+        }
+    }
+    if (person_pixels) {
+        unsigned long long todo = __ballot(mesh >= 0);
+        while (todo) {                                                    // wave-uniform: todo is the same in every lane
+            const int leader = __ffsll((long long)todo) - 1;
+            const int m = __shfl(mesh, leader);
+            const unsigned long long same = __ballot(mesh == m);
+            if ((int)(threadIdx.x & (warpSize - 1)) == leader) atomicAdd(&person_pixels[m], __popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
 
 // ---- rotate_view_weak_perspective (vis_utils.py:26-51) ---------------------------------------------------
 struct ViewCfg {
@@ -401,6 +469,41 @@ int romp_view_weak_perspective(const float* verts, int n, int nver, double rx, d
     hipLaunchKernelGGL(view_rotate_kernel, dim3(grid), dim3(256), 0, st, verts, count, cfg, out, work);
     hipLaunchKernelGGL(view_extent_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, work);
     hipLaunchKernelGGL(view_apply_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, (const unsigned*)work, center_scale);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_sim3dr_maps(const float* verts, int n, int nver, const int32_t* tris, int ntri, int h, int w, const int32_t* mesh_ids,
+                     const float* attrs, int c, float attr_bg, const uint8_t* vert_labels, int32_t* person_map, int32_t* tri_map,
+                     float* bary_map, float* attr_map, uint8_t* label_map, uint8_t* vert_visible, int32_t* person_pixels,
+                     unsigned long long* keys, int keys_ready, void* stream) {
+    ROMP_REQUIRE(verts && tris && keys && n > 0 && nver > 0 && ntri > 0 && h > 0 && w > 0, "romp_sim3dr_maps: bad arguments");
+    ROMP_REQUIRE(!attr_map || (attrs && c >= 1 && c <= 4), "romp_sim3dr_maps: attr_map needs attrs of 1 to 4 channels, got c = %d", c);
+    ROMP_REQUIRE(!label_map || vert_labels, "romp_sim3dr_maps: label_map needs vert_labels");
+    const int mbits = mesh_bits(n);
+    ROMP_REQUIRE((long long)ntri <= (1ll << (32 - mbits)),
+                 "romp_sim3dr_maps: %d meshes leave %d key bits for the triangle index, %d triangles do not fit", n, 32 - mbits,
+                 ntri);
+    hipStream_t st = (hipStream_t)stream;
+    if (!keys_ready) {
+        ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64, (unsigned)std::min(n, kMaxGridY)), dim3(64), 0, st, verts, tris,
+                           ntri, n, nver, mbits, h, w, keys);
+    }
+    if (vert_visible) ROMP_HIP_CHECK(hipMemsetAsync(vert_visible, 0, (size_t)n * nver, st));
+    if (person_pixels) ROMP_HIP_CHECK(hipMemsetAsync(person_pixels, 0, (size_t)n * sizeof(int32_t), st));
+    const dim3 grid((unsigned)(((size_t)h * w + 255) / 256));
+#define ROMP_MAPS_LAUNCH(C)                                                                                                       \
+    hipLaunchKernelGGL(sim3dr_maps_kernel<C>, grid, dim3(256), 0, st, verts, tris, (const unsigned long long*)keys, nver, mbits, h, \
+                       w, mesh_ids, attrs, attr_bg, vert_labels, person_map, tri_map, bary_map, attr_map, label_map, vert_visible,  \
+                       person_pixels)
+    switch (attr_map ? c : 1) {
+        case 1: ROMP_MAPS_LAUNCH(1); break;
+        case 2: ROMP_MAPS_LAUNCH(2); break;
+        case 3: ROMP_MAPS_LAUNCH(3); break;
+        default: ROMP_MAPS_LAUNCH(4); break;
+    }
+#undef ROMP_MAPS_LAUNCH
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

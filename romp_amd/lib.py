@@ -97,6 +97,7 @@ def load():
         'romp_sim3dr_rasterize': (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         'romp_sim3dr_render_batch': (C.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_float), vp, vp, vp, vp]),
         'romp_view_weak_perspective': (C.c_int, [vp, i32, i32, C.c_double, C.c_double, i32, i32, C.c_double, vp, vp, vp, vp]),
+        'romp_sim3dr_maps': (C.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, f, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         'romp_net_load': (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, i32]),
         'romp_net_plan_info': (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
         'romp_net_plan_kind': (C.c_int, [vp, C.POINTER(C.c_int32)]),
@@ -144,6 +145,8 @@ EXPORTS = ['romp_abi_version', 'romp_last_error', 'romp_net_create', 'romp_net_f
            'romp_bev_crowd_merge']
 # added after the 52 exports above, which a test pins by count; same ABI version
 VIEW_EXPORTS = ['romp_sim3dr_render_batch', 'romp_view_weak_perspective']
+# include/romp_hip_maps.h
+MAP_EXPORTS = ['romp_sim3dr_maps']
 
 
 def has_bf16x3():

@@ -22,7 +22,7 @@ from . import lib as L
 from .net import RangeGuard, RompNet
 from .post_parser import (_HAVE_CV2, CenterMap, SMPL_parser, body_mesh_projection2image, convert_cam_to_3d_trans, pnp_translation,
                           parsing_outputs)
-from .vis import rendering_romp_bev_results, setup_renderer
+from .vis import dense_maps, mesh_panel_keys, rendering_romp_bev_results, setup_renderer
 from .utils import ResultSaver, convert_tensor2numpy, determine_device, img_preprocess, img_preprocess_device
 
 
@@ -68,13 +68,16 @@ def romp_settings(input_args=sys.argv[1:]):
     parser.add_argument('--calib_dir', type=str, default=None,
                         help='[romp_amd] calibrate on up to 4 images of this directory (pre-processed like inputs) instead of synthetic frames')
     parser.add_argument('--host_preprocess', action='store_true', help='[romp_amd] pad/resize on the host (cv2 / numpy) instead of the device kernel')
+    parser.add_argument('--dense_maps', action='store_true',
+                        help='[romp_amd] also return per-pixel maps of the mesh panel (person_map, part_map, depth_map) and per-person '
+                             'verts_visible / person_pixels, computed on the device (vis.dense_maps)')
     args = parser.parse_args(input_args)
     if not torch.cuda.is_available():
         args.GPU = -1
         args.temporal_optimize = False
     if args.show:
         args.render_mesh = True
-    if args.render_mesh or args.show_largest:
+    if args.render_mesh or args.show_largest or args.dense_maps:
         args.calc_smpl = True
     if not os.path.exists(args.smpl_path):
         alt = args.smpl_path.replace('SMPL_NEUTRAL.pth', 'smpl_packed_info.pth')
@@ -150,6 +153,8 @@ class ROMP(nn.Module):
         if self.settings.render_mesh:                                                       # main.py:101-103
             self.visualize_items = self.settings.show_items.split(',')
             self.renderer = setup_renderer(name=self.settings.renderer, device=self.tdevice)
+        elif getattr(self.settings, 'dense_maps', False):
+            self.renderer = setup_renderer(device=self.tdevice)
 
     def single_image_forward(self, image):
         """main.py:106-115."""
@@ -208,7 +213,8 @@ class ROMP(nn.Module):
         if self.settings.calc_smpl:
             outputs = self.smpl_parser(outputs, root_align=self.settings.root_align)        # main.py:168
             outputs.update(body_mesh_projection2image(outputs['joints'], outputs['cam'],
-                                                      vertices=outputs['verts'] if self.settings.render_mesh else None,
+                                                      vertices=outputs['verts'] if self.settings.render_mesh or
+                                                      getattr(self.settings, 'dense_maps', False) else None,
                                                       input2org_offsets=image_pad_info))   # main.py:169
         return outputs
 
@@ -279,8 +285,9 @@ class ROMP(nn.Module):
     def forward(self, image, signal_ID=0, **kwargs):
         """main.py:160-176: BGR uint8 HxWx3 numpy -> dict of numpy arrays, or None."""
         s = self.settings
+        dense = getattr(s, 'dense_maps', False)
         if (getattr(self, 'fast_single', True) and s.calc_smpl and not s.temporal_optimize and not s.render_mesh
-                and not getattr(s, 'host_preprocess', False)):
+                and not getattr(s, 'host_preprocess', False) and not dense):
             return self._forward_fast(image)
         outputs, image_pad_info = self.single_image_forward(image)
         if outputs is None:
@@ -288,9 +295,13 @@ class ROMP(nn.Module):
         if self.settings.temporal_optimize:                                                 # main.py:164-165
             outputs = self.temporal_optimization(outputs, signal_ID)
         outputs = self._finish(outputs, image_pad_info)
+        keys = None
         if self.settings.render_mesh:                                                       # main.py:170-172
             rendering_cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': self.settings.renderer}
-            outputs = rendering_romp_bev_results(self.renderer, outputs, image, rendering_cfgs)
+            keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
+            outputs = rendering_romp_bev_results(self.renderer, outputs, image, rendering_cfgs, keys=keys)
+        if dense:                                                                           # the mesh panel's raster pass serves both
+            outputs = dense_maps(self.renderer, outputs, image.shape, self.smpl_parser.smpl_model.part_labels, keys=keys)
         return convert_tensor2numpy(outputs)
 
     @torch.no_grad()

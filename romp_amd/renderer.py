@@ -57,6 +57,29 @@ def _device(device=None):
     return torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
 
 
+def _verts_dev(verts_list, dev):
+    """(n,V,3) float32 on the device from a device tensor, an array or a list of (V,3) arrays."""
+    if torch.is_tensor(verts_list):
+        return verts_list.to(dev, torch.float32).contiguous()
+    if len(verts_list) == 0:
+        return torch.empty((0, 0, 3), dtype=torch.float32, device=dev)
+    return torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in verts_list]))).to(dev)
+
+
+def _keys(keys, h, w, dev):
+    """The rasterizer's h*w 64-bit words: the caller's tensor (checked) or a fresh one."""
+    if keys is None:
+        return torch.empty(h * w, dtype=torch.int64, device=dev)
+    if not (torch.is_tensor(keys) and keys.dtype == torch.int64 and keys.device == dev and keys.is_contiguous() and keys.numel() == h * w):
+        raise ValueError('keys must be a contiguous int64 tensor of %d x %d words on %s' % (h, w, dev))
+    return keys
+
+
+def _dev_array(x, dtype, dev):
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(dev, dtype).contiguous()
+
+
 def get_normal(vertices, triangles, device=None):
     """renderer.py:32-37: per-vertex normals (numpy in, numpy out)."""
     dev = _device(device)
@@ -151,7 +174,8 @@ class Sim3DR(object):
         return amb
 
     def _render_batch(self, img, verts, topo, colors, keys):
-        """Meshes verts (n,V,3) (device) painted in index order onto img (h,w,3) (device, in place): one fixed set of launches."""
+        """Meshes verts (n,V,3) (device) painted in index order onto img (h,w,3) (device, in place): one fixed set of launches.
+        Returns `keys`, which now hold every pixel's winner: `maps(..., keys=keys)` reads them instead of rasterizing again."""
         dev = img.device
         n = verts.shape[0]
         amb = torch.from_numpy(self._ambient(colors)).pin_memory().to(dev, non_blocking=True)   # no stream sync
@@ -161,9 +185,12 @@ class Sim3DR(object):
                                                       topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(amb),
                                                       self._light_cfg(colors[:1]), L.ptr(normals), L.ptr(light), L.ptr(keys),
                                                       L.stream_ptr(dev)))
+        return keys
 
-    def __call__(self, verts_list, triangles, bg, mesh_colors=np.array([[1, 0.6, 0.4]])):
-        """`bg`: numpy (h,w,3) uint8, or a device tensor (a canvas made on the device); neither is modified."""
+    def __call__(self, verts_list, triangles, bg, mesh_colors=np.array([[1, 0.6, 0.4]]), keys=None):
+        """`bg`: numpy (h,w,3) uint8, or a device tensor (a canvas made on the device); neither is modified.  `keys`: an int64
+        device tensor of h*w words to rasterize into (default: a fresh one); with one topology and at least one mesh it holds
+        the winners of this very picture afterwards, for `maps(..., keys=keys)`."""
         dev = _device(self.device)
         if torch.is_tensor(bg):
             img = bg.to(dev, torch.uint8).clone(memory_format=torch.contiguous_format)
@@ -171,11 +198,8 @@ class Sim3DR(object):
             img = torch.from_numpy(np.ascontiguousarray(bg)).to(dev)        # a copy: the reference returns bg.copy()
         if img.dim() != 3 or img.shape[2] != 3:
             raise ValueError('Sim3DR paints (h, w, 3) images, got %s' % (tuple(img.shape),))
-        keys = torch.empty(img.shape[0] * img.shape[1], dtype=torch.int64, device=dev)
-        if torch.is_tensor(verts_list):
-            verts_dev = verts_list.to(dev, torch.float32).contiguous()
-        else:
-            verts_dev = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(v, np.float32) for v in verts_list]))).to(dev)
+        keys = _keys(keys, img.shape[0], img.shape[1], dev)
+        verts_dev = _verts_dev(verts_list, dev)
         n = len(verts_dev)
         if n == 0:
             return img.cpu().numpy()
@@ -188,6 +212,73 @@ class Sim3DR(object):
                 self._render_batch(img, verts_dev[ind:ind + 1], _topology(triangles[ind], verts_dev.shape[1], dev), colors[ind:ind + 1],
                                    keys)
         return img.cpu().numpy()
+
+    MAPS = ('person_map', 'tri_map', 'bary_map', 'attr_map', 'label_map', 'vert_visible', 'person_pixels')
+
+    def maps(self, verts_list, triangles, image_shape, mesh_ids=None, attrs=None, attr_bg=0., vert_labels=None, want=None, keys=None):
+        """What `__call__` decides per pixel, kept instead of painted (romp_sim3dr_maps, include/romp_hip_maps.h): the meshes
+        verts_list (n,V,3) of ONE topology are painted in index order onto an image_shape[:2] = (h, w) canvas, each with a
+        fresh z-buffer, so a pixel's winner is the highest mesh that covers it, inside that mesh the fragment of greatest
+        depth, the lowest triangle on equal depth -- the fragment whose colour `__call__` shows.  Returns a dict of device
+        tensors, the names of `want` (default: every map the inputs allow):
+          person_map (h,w) int32: mesh_ids[mesh] (default: the mesh index), -1 on the background;
+          tri_map (h,w) int32: the winning triangle, -1;
+          bary_map (h,w,3) float32: its weights (w0,w1,w2) at the pixel, 0;
+          attr_map (h,w,c) float32: (w0*a0 + w1*a1) + w2*a2 of the per-vertex attribute attrs (n,V,c), c <= 4 ((n,V): c = 1),
+            attr_bg on the background.  The interpolation is affine in screen space, as the reference's depth buffer is, not
+            perspective-correct: attrs = verts[..., 2:] reproduces that buffer, camera-space z gives metric depth, template
+            coordinates a canonical-surface map;
+          label_map (h,w) uint8: vert_labels (V,) at the winner's corner of greatest weight (the lowest corner on ties), 255;
+          vert_visible (n,V) uint8: 1 iff the vertex is a corner of a triangle that wins at least one pixel;
+          person_pixels (n,) int32: the number of pixels each mesh wins.
+        Numpy or device input, as in `__call__`.  `keys`: the tensor a `__call__(..., keys=keys)` on these very meshes,
+        triangles and canvas size has just filled: the raster pass is not run again.  No mesh: all background, no launch."""
+        dev = _device(self.device)
+        h, w = int(image_shape[0]), int(image_shape[1])
+        verts = _verts_dev(verts_list, dev)
+        if verts.dim() != 3 or verts.shape[2] != 3:
+            raise ValueError('Sim3DR.maps takes (n, V, 3) vertices, got %s' % (tuple(verts.shape),))
+        n, nver = verts.shape[:2]
+        if n and len(np.shape(triangles)) != 2:
+            raise ValueError('Sim3DR.maps needs one triangle table (ntri, 3) for all meshes, got a list of topologies')
+        if attrs is not None:
+            attrs = _dev_array(attrs, torch.float32, dev)
+            attrs = attrs.unsqueeze(-1) if attrs.dim() == 2 else attrs
+            if attrs.dim() != 3 or tuple(attrs.shape[:2]) != (n, nver) or not 1 <= attrs.shape[2] <= 4:
+                raise ValueError('attrs must be (%d, %d, c) with 1 <= c <= 4, got %s' % (n, nver, tuple(attrs.shape)))
+        if vert_labels is not None:
+            vert_labels = _dev_array(vert_labels, torch.uint8, dev).reshape(-1)
+            if n and vert_labels.numel() != nver:
+                raise ValueError('vert_labels must hold %d labels, got %d' % (nver, vert_labels.numel()))
+        if mesh_ids is not None:
+            mesh_ids = _dev_array(mesh_ids, torch.int32, dev).reshape(-1)
+            if mesh_ids.numel() != n:
+                raise ValueError('mesh_ids must hold %d ids, got %d' % (n, mesh_ids.numel()))
+        if want is None:
+            want = [m for m in self.MAPS if (m != 'attr_map' or attrs is not None) and (m != 'label_map' or vert_labels is not None)]
+        want = list(want)
+        unknown = [m for m in want if m not in self.MAPS]
+        if unknown:
+            raise ValueError('unknown maps %s (known: %s)' % (unknown, ', '.join(self.MAPS)))
+        if 'attr_map' in want and attrs is None:
+            raise ValueError('attr_map needs attrs')
+        if 'label_map' in want and vert_labels is None:
+            raise ValueError('label_map needs vert_labels')
+        c = attrs.shape[2] if attrs is not None else 1
+        spec = {'person_map': ((h, w), torch.int32, -1), 'tri_map': ((h, w), torch.int32, -1), 'bary_map': ((h, w, 3), torch.float32, 0.),
+                'attr_map': ((h, w, c), torch.float32, float(attr_bg)), 'label_map': ((h, w), torch.uint8, 255),
+                'vert_visible': ((n, nver), torch.uint8, 0), 'person_pixels': ((n,), torch.int32, 0)}
+        if n == 0:
+            return {m: torch.full(spec[m][0], spec[m][2], dtype=spec[m][1], device=dev) for m in want}
+        topo = _topology(triangles, nver, dev)
+        ready = keys is not None
+        keys = _keys(keys, h, w, dev)
+        out = {m: torch.empty(spec[m][0], dtype=spec[m][1], device=dev) for m in want}
+        with torch.cuda.device(dev):
+            L.check(L.load().romp_sim3dr_maps(L.ptr(verts), n, nver, L.ptr(topo.tri), topo.ntri, h, w, L.ptr(mesh_ids), L.ptr(attrs), c,
+                                              float(attr_bg), L.ptr(vert_labels), *[L.ptr(out.get(m)) for m in self.MAPS], L.ptr(keys),
+                                              int(ready), L.stream_ptr(dev)))
+        return out
 
 
 def view_weak_perspective(verts, rx, ry, img_shape, expand_ratio=1.2):

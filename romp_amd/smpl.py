@@ -30,6 +30,10 @@ class SMPL(nn.Module):
         self.register_buffer('posedirs', model_info['posedirs'].float())
         self.register_buffer('parents', model_info['kintree_table'].long())
         self.register_buffer('lbs_weights', model_info['weights'].float())
+        # body part of every vertex: the joint of greatest skinning weight (the first on ties), uint8 in 0..23 (not saved with
+        # the module's state: it follows from `weights`)
+        labels = np.argmax(model_info['weights'].float().cpu().numpy(), axis=1).astype(np.uint8)
+        self.register_buffer('part_labels', torch.from_numpy(labels), persistent=False)
         self._ctx = None
         self._ctx_device = None
 
