@@ -56,6 +56,9 @@ def bev_settings(input_args=sys.argv[1:]):
     p.add_argument('--renderer', type=str, default='sim3dr')
     p.add_argument('--show_items', type=str, default='mesh',
                    help='any of mesh, mesh_bird_view, mesh_side_view (panels in that order); the cv2 overlays are not supported')
+    p.add_argument('--mesh_color', type=str, default='identity', choices=['identity', 'same', 'track_id', 'part'],
+                   help='[romp_amd] how --render_mesh colours the meshes: identity: per person, left to right (default); same: one colour; '
+                        'track_id: per person by track id, stable across frames with -t; part: per vertex by SMPL body part')
     p.add_argument('-sc', '--smooth_coeff', type=float, default=3.)
     p.add_argument('--show', action='store_true')
     p.add_argument('--smpl_path', type=str, default=osp.join(osp.expanduser('~'), '.romp', 'SMPLA_NEUTRAL.pth'))
@@ -433,7 +436,8 @@ class BEV(nn.Module):
         keys = None
         if self.settings.render_mesh:
             keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
-            cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': getattr(self.settings, 'renderer', 'sim3dr')}
+            cfgs = {'mesh_color': getattr(self.settings, 'mesh_color', 'identity'), 'items': self.visualize_items,
+                    'renderer': getattr(self.settings, 'renderer', 'sim3dr'), 'part_labels': self.smpl_parser.smpl_model.part_labels}
             res = rendering_romp_bev_results(self.renderer, res, image, cfgs, keys=keys)
         if dense:
             res = dense_maps(self.renderer, res, image.shape, self.smpl_parser.smpl_model.part_labels, keys=keys)

@@ -64,20 +64,26 @@ struct LightCfg {
     float ambient[3];          // intensity_ambient * color, already rounded to float32 as numpy does (renderer.py:83)
     float i_dir, i_spec;       // 0: term switched off
     float color_dir[3], light_pos[3], view_pos[3];
+    int spec_exp;              // specular_exp >= 1 (renderer.py:110); 1: the reference default
 };
 
 __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
 // renderer.py:19-24 (norm_vertices) + :77-110.  One workgroup per mesh (v / nrm / light: n x nver x 3);
-// ambient: n x 3 per-mesh ambient terms (device), or null for cfg.ambient.
+// ambient: n x 3 per-mesh ambient terms (device), or null for cfg.ambient.  texture: n x nver x 3 per-vertex colours, or
+// null; with it the output is texture * light (renderer.py:124: one rounded multiply of the clipped light), without it
+// the clipped light itself.  cfg.spec_exp = e: each component of v2v * reflection is raised to e before the three are
+// summed (renderer.py:110).  e = 1 multiplies nothing; e >= 2 is t * t * ... * t, e - 1 rounded multiplies from left to
+// right: numpy's square for e = 2, within rounding of its powf for e > 2 (not bit for bit).
 __global__ __launch_bounds__(1024) void sim3dr_light_kernel(const float* __restrict__ v, const float* __restrict__ nrm, int nver,
                                                              LightCfg cfg, const float* __restrict__ ambient,
-                                                             float* __restrict__ light) {
+                                                             const float* __restrict__ texture, float* __restrict__ light) {
     __shared__ float red[3][1024];
     __shared__ float s_min[3], s_max1, s_max3[3];
     const int tid = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * nver * 3;
     v += base; nrm += base; light += base;
+    if (texture) texture += base;
     const float amb[3] = {ambient ? ambient[3 * blockIdx.x] : cfg.ambient[0], ambient ? ambient[3 * blockIdx.x + 1] : cfg.ambient[1],
                           ambient ? ambient[3 * blockIdx.x + 2] : cfg.ambient[2]};
     float m[3] = {3.4e38f, 3.4e38f, 3.4e38f};
@@ -136,14 +142,19 @@ __global__ __launch_bounds__(1024) void sim3dr_light_kernel(const float* __restr
                 float spe = 0.f;
                 for (int k = 0; k < 3; ++k) {
                     const float r = (2.f * cs) * n[k] - d[k];
-                    const float t = (e[k] / el) * r;
+                    const float t1 = (e[k] / el) * r;
+                    float t = t1;
+                    for (int p = 1; p < cfg.spec_exp; ++p) t = t * t1;
                     spe = k == 0 ? t : spe + t;
                 }
                 spe = cs != 0.f ? clip01(spe) : 0.f;
                 for (int k = 0; k < 3; ++k) l[k] += (cfg.i_spec * cfg.color_dir[k]) * clip01(spe);
             }
         }
-        for (int k = 0; k < 3; ++k) light[3 * i + k] = clip01(l[k]);
+        for (int k = 0; k < 3; ++k) {
+            const float lk = clip01(l[k]);
+            light[3 * i + k] = texture ? texture[3 * i + k] * lk : lk;
+        }
     }
 }
 
@@ -377,8 +388,9 @@ using namespace romp;
 
 namespace {
 
-LightCfg light_cfg(const float* cfg_host) {
+LightCfg light_cfg(const float* cfg_host, int spec_exp = 1) {
     LightCfg c;
+    c.spec_exp = spec_exp;
     for (int k = 0; k < 3; ++k) {
         c.ambient[k] = cfg_host[k]; c.color_dir[k] = cfg_host[5 + k]; c.light_pos[k] = cfg_host[8 + k]; c.view_pos[k] = cfg_host[11 + k];
     }
@@ -393,6 +405,30 @@ int mesh_bits(int n) {                                                     // ce
 }
 
 constexpr int kMaxGridY = 65535;
+
+// romp_sim3dr_render_batch (textures = null, spec_exp = 1) and romp_sim3dr_render_batch_tex: normals, light, raster, resolve
+int render_batch(const char* who, unsigned char* image, int h, int w, const float* verts, int n, int nver, const int32_t* tris,
+                 int ntri, const int32_t* adj_off, const int32_t* adj_ent, const float* ambient, const float* cfg_host,
+                 const float* textures, int spec_exp, float* normals, float* light, unsigned long long* keys, void* stream) {
+    ROMP_REQUIRE(image && verts && tris && adj_off && adj_ent && ambient && cfg_host && normals && light && keys && n > 0 &&
+                 nver > 0 && ntri > 0 && h > 0 && w > 0, "%s: bad arguments", who);
+    const int mbits = mesh_bits(n);
+    ROMP_REQUIRE((long long)ntri <= (1ll << (32 - mbits)),
+                 "%s: %d meshes leave %d key bits for the triangle index, %d triangles do not fit", who, n, 32 - mbits, ntri);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gy = (unsigned)std::min(n, kMaxGridY);
+    hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256, gy), dim3(256), 0, st, verts, tris, adj_off, adj_ent, nver, n,
+                       normals);
+    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(n), dim3(1024), 0, st, verts, normals, nver, light_cfg(cfg_host, spec_exp), ambient,
+                       textures, light);
+    ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64, gy), dim3(64), 0, st, verts, tris, ntri, n, nver, mbits, h, w,
+                       keys);
+    hipLaunchKernelGGL(sim3dr_resolve_kernel, dim3((h * w + 255) / 256), dim3(256), 0, st, verts, tris, light, keys, nver, mbits, h,
+                       w, 3, 0, image);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
 
 }  // namespace
 
@@ -410,7 +446,17 @@ int romp_sim3dr_normals(const float* verts, const int32_t* tris, const int32_t* 
 int romp_sim3dr_light(const float* verts, const float* normals, int nver, const float* cfg_host, float* light, void* stream) {
     ROMP_REQUIRE(verts && normals && cfg_host && light && nver > 0, "romp_sim3dr_light: bad arguments");
     hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver, light_cfg(cfg_host),
-                       (const float*)nullptr, light);
+                       (const float*)nullptr, (const float*)nullptr, light);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_sim3dr_light_tex(const float* verts, const float* normals, int nver, const float* cfg_host, int specular_exp,
+                          const float* texture, float* light, void* stream) {
+    ROMP_REQUIRE(verts && normals && cfg_host && light && nver > 0, "romp_sim3dr_light_tex: bad arguments");
+    ROMP_REQUIRE(specular_exp >= 1, "romp_sim3dr_light_tex: specular_exp must be an integer >= 1, got %d", specular_exp);
+    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver,
+                       light_cfg(cfg_host, specular_exp), (const float*)nullptr, texture, light);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -431,24 +477,17 @@ int romp_sim3dr_rasterize(unsigned char* image, const float* verts, const int32_
 int romp_sim3dr_render_batch(unsigned char* image, int h, int w, const float* verts, int n, int nver, const int32_t* tris,
                              int ntri, const int32_t* adj_off, const int32_t* adj_ent, const float* ambient,
                              const float* cfg_host, float* normals, float* light, unsigned long long* keys, void* stream) {
-    ROMP_REQUIRE(image && verts && tris && adj_off && adj_ent && ambient && cfg_host && normals && light && keys && n > 0 &&
-                 nver > 0 && ntri > 0 && h > 0 && w > 0, "romp_sim3dr_render_batch: bad arguments");
-    const int mbits = mesh_bits(n);
-    ROMP_REQUIRE((long long)ntri <= (1ll << (32 - mbits)),
-                 "romp_sim3dr_render_batch: %d meshes leave %d key bits for the triangle index, %d triangles do not fit", n,
-                 32 - mbits, ntri);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned gy = (unsigned)std::min(n, kMaxGridY);
-    hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256, gy), dim3(256), 0, st, verts, tris, adj_off, adj_ent, nver, n,
-                       normals);
-    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(n), dim3(1024), 0, st, verts, normals, nver, light_cfg(cfg_host), ambient, light);
-    ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64, gy), dim3(64), 0, st, verts, tris, ntri, n, nver, mbits, h, w,
-                       keys);
-    hipLaunchKernelGGL(sim3dr_resolve_kernel, dim3((h * w + 255) / 256), dim3(256), 0, st, verts, tris, light, keys, nver, mbits, h,
-                       w, 3, 0, image);
-    ROMP_HIP_CHECK(hipGetLastError());
-    return ROMP_OK;
+    return render_batch("romp_sim3dr_render_batch", image, h, w, verts, n, nver, tris, ntri, adj_off, adj_ent, ambient, cfg_host,
+                        nullptr, 1, normals, light, keys, stream);
+}
+
+int romp_sim3dr_render_batch_tex(unsigned char* image, int h, int w, const float* verts, int n, int nver, const int32_t* tris,
+                                 int ntri, const int32_t* adj_off, const int32_t* adj_ent, const float* ambient,
+                                 const float* cfg_host, const float* textures, int specular_exp, float* normals, float* light,
+                                 unsigned long long* keys, void* stream) {
+    ROMP_REQUIRE(specular_exp >= 1, "romp_sim3dr_render_batch_tex: specular_exp must be an integer >= 1, got %d", specular_exp);
+    return render_batch("romp_sim3dr_render_batch_tex", image, h, w, verts, n, nver, tris, ntri, adj_off, adj_ent, ambient,
+                        cfg_host, textures, specular_exp, normals, light, keys, stream);
 }
 
 int romp_view_weak_perspective(const float* verts, int n, int nver, double rx, double ry, int img_h, int img_w,

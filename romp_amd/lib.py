@@ -96,6 +96,9 @@ def load():
         'romp_sim3dr_light': (C.c_int, [vp, vp, i32, C.POINTER(C.c_float), vp, vp]),
         'romp_sim3dr_rasterize': (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         'romp_sim3dr_render_batch': (C.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_float), vp, vp, vp, vp]),
+        'romp_sim3dr_light_tex': (C.c_int, [vp, vp, i32, C.POINTER(C.c_float), i32, vp, vp, vp]),
+        'romp_sim3dr_render_batch_tex': (C.c_int, [vp, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, C.POINTER(C.c_float), vp, i32, vp, vp,
+                                                   vp, vp]),
         'romp_view_weak_perspective': (C.c_int, [vp, i32, i32, C.c_double, C.c_double, i32, i32, C.c_double, vp, vp, vp, vp]),
         'romp_sim3dr_maps': (C.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, f, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         'romp_net_load': (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, i32]),
@@ -147,6 +150,8 @@ EXPORTS = ['romp_abi_version', 'romp_last_error', 'romp_net_create', 'romp_net_f
 VIEW_EXPORTS = ['romp_sim3dr_render_batch', 'romp_view_weak_perspective']
 # include/romp_hip_maps.h
 MAP_EXPORTS = ['romp_sim3dr_maps']
+# include/romp_hip_views.h: per-vertex colours and the specular exponent
+TEXTURE_EXPORTS = ['romp_sim3dr_light_tex', 'romp_sim3dr_render_batch_tex']
 
 
 def has_bf16x3():

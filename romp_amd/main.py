@@ -22,7 +22,7 @@ from . import lib as L
 from .net import RangeGuard, RompNet
 from .post_parser import (_HAVE_CV2, CenterMap, SMPL_parser, body_mesh_projection2image, convert_cam_to_3d_trans, pnp_translation,
                           parsing_outputs)
-from .vis import dense_maps, mesh_panel_keys, rendering_romp_bev_results, setup_renderer
+from .vis import MESH_COLOR_MODES, dense_maps, mesh_panel_keys, rendering_romp_bev_results, setup_renderer
 from .utils import ResultSaver, convert_tensor2numpy, determine_device, img_preprocess, img_preprocess_device
 
 
@@ -44,6 +44,10 @@ def romp_settings(input_args=sys.argv[1:]):
     parser.add_argument('--show', action='store_true', help='Whether to show the rendered results')
     parser.add_argument('--show_items', type=str, default='mesh',
                         help='The items to visualized: any of mesh, mesh_bird_view, mesh_side_view (panels in that order)')
+    parser.add_argument('--mesh_color', type=str, default='identity', choices=list(MESH_COLOR_MODES),
+                        help='[romp_amd] how --render_mesh colours the meshes: identity: per person, left to right (default); same: one colour; '
+                             'track_id: per person by track id, stable across frames with -t (left to right without track ids); '
+                             'part: per vertex by SMPL body part')
     parser.add_argument('--save_video', action='store_true', help='Whether to save the video results')
     parser.add_argument('--frame_rate', type=int, default=24, help='The frame_rate of saved video results')
     parser.add_argument('--smpl_path', type=str, default=osp.join(osp.expanduser("~"), '.romp', 'SMPL_NEUTRAL.pth'), help='The path of smpl model file')
@@ -297,7 +301,8 @@ class ROMP(nn.Module):
         outputs = self._finish(outputs, image_pad_info)
         keys = None
         if self.settings.render_mesh:                                                       # main.py:170-172
-            rendering_cfgs = {'mesh_color': 'identity', 'items': self.visualize_items, 'renderer': self.settings.renderer}
+            rendering_cfgs = {'mesh_color': getattr(self.settings, 'mesh_color', 'identity'), 'items': self.visualize_items,
+                              'renderer': self.settings.renderer, 'part_labels': self.smpl_parser.smpl_model.part_labels}
             keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
             outputs = rendering_romp_bev_results(self.renderer, outputs, image, rendering_cfgs, keys=keys)
         if dense:                                                                           # the mesh panel's raster pass serves both

@@ -2,6 +2,8 @@
 (``renderer.py``: ``Sim3DR``, ``rasterize``, ``get_normal``; the Cython extension ``Sim3DR_Cython`` is
 replaced by ``romp_sim3dr_*`` in libromp_hip.so, csrc/render.hip) and ``vis_utils.rotate_view_weak_perspective``
 (``view_weak_perspective``).  Images are bit-identical to the reference's (tests/test_render.py, test_render_views.py).  No CPU path: a missing HIP device / extension raises.
+Per-vertex colours (``render(texture=...)``, ``__call__(vert_colors=...)``) and ``specular_exp`` 2 are bit-identical too; a
+larger exponent is formed by repeated multiplication, within one grey level of numpy's powf (tests/test_gpu_render_texture.py).
 """
 import ctypes as C
 
@@ -117,7 +119,9 @@ def rasterize(vertices, triangles, colors, bg=None, height=None, width=None, cha
 class Sim3DR(object):
     """renderer.py:64-133.  `__call__(verts_list, triangles, bg, mesh_colors)` paints the meshes one after the
     other (each with a fresh z-buffer) onto a copy of `bg` and returns the uint8 image.  Meshes of one topology go
-    through romp_sim3dr_render_batch together: the number of launches does not grow with the number of meshes."""
+    through romp_sim3dr_render_batch together: the number of launches does not grow with the number of meshes.
+    `specular_exp`: any integer >= 1 (the reference default is 1); the device raises v2v * reflection to it by repeated
+    multiplication, which is numpy's result for 1 and 2 and within rounding of it above."""
 
     def __init__(self, **kwargs):
         self.intensity_ambient = convert_type(kwargs.get('intensity_ambient', 0.66))
@@ -128,8 +132,11 @@ class Sim3DR(object):
         self.light_pos = convert_type(kwargs.get('light_pos', (0, 0, -5)))
         self.view_pos = convert_type(kwargs.get('view_pos', (0, 0, 5)))
         self.device = kwargs.get('device', None)
-        if self.specular_exp != 1:
-            raise NotImplementedError('specular_exp != 1 is not on the device path (the reference default is 1)')
+        e = self.specular_exp
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < 1:
+            raise NotImplementedError('specular_exp must be an integer >= 1 on the device path (it multiplies repeatedly; '
+                                      'a fractional or smaller exponent is not supported), got %r' % (e,))
+        self.specular_exp = int(e)
 
     def update_light_pos(self, light_pos):
         self.light_pos = convert_type(light_pos)
@@ -146,23 +153,32 @@ class Sim3DR(object):
                               np.asarray(self.light_pos, np.float32).reshape(3), np.asarray(self.view_pos, np.float32).reshape(3)])
         return (C.c_float * 14)(*[float(x) for x in cfg.astype(np.float32)])
 
-    def _render_dev(self, img, v, topo, color, keys, light):
+    def _render_dev(self, img, v, topo, color, keys, light, texture=None):
         lib = L.load()
         st = L.stream_ptr(img.device)
         normal = torch.empty_like(v)
         L.check(lib.romp_sim3dr_normals(L.ptr(v), L.ptr(topo.tri), L.ptr(topo.adj_off), L.ptr(topo.adj_ent), topo.nver, L.ptr(normal), st))
-        L.check(lib.romp_sim3dr_light(L.ptr(v), L.ptr(normal), topo.nver, self._light_cfg(color), L.ptr(light), st))
+        if texture is None and self.specular_exp == 1:
+            L.check(lib.romp_sim3dr_light(L.ptr(v), L.ptr(normal), topo.nver, self._light_cfg(color), L.ptr(light), st))
+        else:
+            L.check(lib.romp_sim3dr_light_tex(L.ptr(v), L.ptr(normal), topo.nver, self._light_cfg(color), self.specular_exp,
+                                              L.ptr(texture), L.ptr(light), st))
         _rasterize_dev(img, v, topo, light, False, keys)
 
     def render(self, vertices, triangles, bg, color=np.array([[1, 0.6, 0.4]]), texture=None):
-        """renderer.py:76-118 for one mesh (numpy in; `bg` is modified in place and returned)."""
-        if texture is not None:
-            raise NotImplementedError('textured rendering is not on the device path')
+        """renderer.py:76-118 for one mesh (numpy in; `bg` is modified in place and returned).  `texture`: (V,3) floats, one
+        colour per vertex (taken as float32): the mesh is painted with texture * light, light lit with `color` as the
+        ambient colour.  The reference scales the caller's `texture` array in place (`texture *= light`); this one leaves
+        it untouched."""
         dev = _device(self.device)
         img = torch.from_numpy(np.ascontiguousarray(bg)).to(dev)
         v = torch.from_numpy(np.ascontiguousarray(vertices, np.float32)).to(dev)
+        if texture is not None:
+            texture = _dev_array(texture, torch.float32, dev)
+            if tuple(texture.shape) != tuple(v.shape):
+                raise ValueError('texture must be %s like the vertices, got %s' % (tuple(v.shape), tuple(texture.shape)))
         keys = torch.empty(img.shape[0] * img.shape[1], dtype=torch.int64, device=dev)
-        self._render_dev(img, v, _topology(triangles, v.shape[0], dev), color, keys, torch.empty_like(v))
+        self._render_dev(img, v, _topology(triangles, v.shape[0], dev), color, keys, torch.empty_like(v), texture)
         bg[...] = img.cpu().numpy()
         return bg
 
@@ -173,22 +189,34 @@ class Sim3DR(object):
             amb += self.intensity_ambient * np.array(colors)
         return amb
 
-    def _render_batch(self, img, verts, topo, colors, keys):
+    def _render_batch(self, img, verts, topo, colors, keys, textures=None):
         """Meshes verts (n,V,3) (device) painted in index order onto img (h,w,3) (device, in place): one fixed set of launches.
+        textures: (n,V,3) float32 (device) per-vertex colours or None.  Without them and with specular_exp 1 this is
+        romp_sim3dr_render_batch, as before; otherwise romp_sim3dr_render_batch_tex, the same launches.
         Returns `keys`, which now hold every pixel's winner: `maps(..., keys=keys)` reads them instead of rasterizing again."""
         dev = img.device
         n = verts.shape[0]
         amb = torch.from_numpy(self._ambient(colors)).pin_memory().to(dev, non_blocking=True)   # no stream sync
         normals, light = torch.empty_like(verts), torch.empty_like(verts)
+        lib = L.load()
         with torch.cuda.device(dev):
-            L.check(L.load().romp_sim3dr_render_batch(L.ptr(img), img.shape[0], img.shape[1], L.ptr(verts), n, topo.nver, L.ptr(topo.tri),
-                                                      topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(amb),
-                                                      self._light_cfg(colors[:1]), L.ptr(normals), L.ptr(light), L.ptr(keys),
-                                                      L.stream_ptr(dev)))
+            if textures is None and self.specular_exp == 1:
+                L.check(lib.romp_sim3dr_render_batch(L.ptr(img), img.shape[0], img.shape[1], L.ptr(verts), n, topo.nver, L.ptr(topo.tri),
+                                                     topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(amb),
+                                                     self._light_cfg(colors[:1]), L.ptr(normals), L.ptr(light), L.ptr(keys),
+                                                     L.stream_ptr(dev)))
+            else:
+                L.check(lib.romp_sim3dr_render_batch_tex(L.ptr(img), img.shape[0], img.shape[1], L.ptr(verts), n, topo.nver,
+                                                         L.ptr(topo.tri), topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(amb),
+                                                         self._light_cfg(colors[:1]), L.ptr(textures), self.specular_exp,
+                                                         L.ptr(normals), L.ptr(light), L.ptr(keys), L.stream_ptr(dev)))
         return keys
 
-    def __call__(self, verts_list, triangles, bg, mesh_colors=np.array([[1, 0.6, 0.4]]), keys=None):
-        """`bg`: numpy (h,w,3) uint8, or a device tensor (a canvas made on the device); neither is modified.  `keys`: an int64
+    def __call__(self, verts_list, triangles, bg, mesh_colors=np.array([[1, 0.6, 0.4]]), vert_colors=None, keys=None):
+        """`bg`: numpy (h,w,3) uint8, or a device tensor (a canvas made on the device); neither is modified.  `vert_colors`:
+        (n,V,3) floats, numpy or a device tensor, one colour per vertex: mesh i is painted with vert_colors[i] * light_i, its
+        light lit with row i of `mesh_colors` as the ambient colour -- what `render(color=..., texture=...)` paints for each
+        mesh in turn, in one batched call; None: light_i alone, as the reference.  `keys`: an int64
         device tensor of h*w words to rasterize into (default: a fresh one); with one topology and at least one mesh it holds
         the winners of this very picture afterwards, for `maps(..., keys=keys)`."""
         dev = _device(self.device)
@@ -201,16 +229,21 @@ class Sim3DR(object):
         keys = _keys(keys, img.shape[0], img.shape[1], dev)
         verts_dev = _verts_dev(verts_list, dev)
         n = len(verts_dev)
+        if vert_colors is not None:
+            vert_colors = _dev_array(vert_colors, torch.float32, dev)
+            if vert_colors.dim() != 3 or vert_colors.shape[0] != n or (n and tuple(vert_colors.shape) != tuple(verts_dev.shape)):
+                raise ValueError('vert_colors must be (n, V, 3) like the vertices %s, got %s'
+                                 % (tuple(verts_dev.shape), tuple(vert_colors.shape)))
         if n == 0:
             return img.cpu().numpy()
         palette = np.asarray(mesh_colors)
         colors = palette[np.arange(n) % len(palette)]
         if len(np.shape(triangles)) == 2:                                    # one topology: every mesh in one batch
-            self._render_batch(img, verts_dev, _topology(triangles, verts_dev.shape[1], dev), colors, keys)
+            self._render_batch(img, verts_dev, _topology(triangles, verts_dev.shape[1], dev), colors, keys, vert_colors)
         else:
             for ind in range(n):
                 self._render_batch(img, verts_dev[ind:ind + 1], _topology(triangles[ind], verts_dev.shape[1], dev), colors[ind:ind + 1],
-                                   keys)
+                                   keys, None if vert_colors is None else vert_colors[ind:ind + 1])
         return img.cpu().numpy()
 
     MAPS = ('person_map', 'tri_map', 'bary_map', 'attr_map', 'label_map', 'vert_visible', 'person_pixels')

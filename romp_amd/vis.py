@@ -1,6 +1,6 @@
 """Mesh visualisation glue -- mirror of ``simple_romp/vis_human/main.py`` for the Sim3DR renderer
 (``setup_renderer`` :11-21, ``rendering_romp_bev_results`` :23-113, items 'mesh', 'mesh_bird_view',
-'mesh_side_view') and of ``vis_utils.mesh_color_left2right`` (:147-153).  The view transform and the
+'mesh_side_view') and of ``vis_utils.mesh_color_left2right`` (:147-153) and ``mesh_color_trackID`` (:238-241).  The view transform and the
 rasterization run on the device (renderer.py here); pyrender / open3d back-ends and the cv2 overlays
 (pj2d, j3d, center_conf, tracking) are not part of the MI355X path."""
 import numpy as np
@@ -13,6 +13,30 @@ color_table_default = np.array([
     [0.4, 0.6, 1], [0.8, 0.7, 1], [0.1, 0.9, 1], [0.8, 0.9, 1], [1, 0.6, 0.4], [1, 0.7, 0.8], [1, 0.9, 0.1],
     [1, 0.9, 0.8], [0.9, 1, 1], [0.9, 0.7, 0.4], [0.8, 0.7, 1], [0.8, 0.9, 1], [0.9, 0.3, 0.1], [0.7, 1, 0.6],
     [0.7, 0.4, 0.6], [0.3, 0.5, 1]])[:, ::-1]
+
+
+# vis_utils.py:155-236 -- the 79 colours persons are coloured with by track id (the detection-toolkit colour list), float32
+tracking_color_list = np.array(
+    [[0.000, 0.447, 0.741], [0.850, 0.325, 0.098], [0.929, 0.694, 0.125], [0.494, 0.184, 0.556], [0.466, 0.674, 0.188],
+     [0.301, 0.745, 0.933], [0.635, 0.078, 0.184], [0.300, 0.300, 0.300], [0.600, 0.600, 0.600], [1.000, 0.000, 0.000],
+     [1.000, 0.500, 0.000], [0.749, 0.749, 0.000], [0.000, 1.000, 0.000], [0.000, 0.000, 1.000], [0.667, 0.000, 1.000]]
+    + [[r, g, 0.000] for r in (0.333, 0.667, 1.000) for g in (0.333, 0.667, 1.000)]
+    + [[r, g, 0.500] for r in (0.000, 0.333, 0.667, 1.000) for g in (0.000, 0.333, 0.667, 1.000)][1:]
+    + [[r, g, 1.000] for r in (0.000, 0.333, 0.667, 1.000) for g in (0.000, 0.333, 0.667, 1.000)][1:-1]
+    + [[x, 0.000, 0.000] for x in (0.167, 0.333, 0.500, 0.667, 0.833, 1.000)]
+    + [[0.000, x, 0.000] for x in (0.167, 0.333, 0.500, 0.667, 0.833, 1.000)]
+    + [[0.000, 0.000, x] for x in (0.167, 0.333, 0.500, 0.667, 0.833, 1.000)]
+    + [[x, x, x] for x in (0.000, 0.143, 0.286, 0.429, 0.571, 0.714, 0.857, 1.000)], np.float32)
+
+# [romp_amd] mesh_color 'part': one colour per SMPL body part (SMPL.part_labels, 0..23), picked by hand so that the rows
+# are distinct and consecutive labels contrast; all in [0, 1]
+part_palette = np.array([
+    [0.90, 0.30, 0.30], [0.30, 0.75, 0.45], [0.35, 0.45, 0.90], [0.95, 0.80, 0.25], [0.70, 0.35, 0.85], [0.25, 0.80, 0.85],
+    [0.95, 0.55, 0.20], [0.55, 0.85, 0.30], [0.90, 0.40, 0.70], [0.35, 0.60, 0.60], [0.65, 0.50, 0.35], [0.50, 0.55, 0.95],
+    [0.80, 0.20, 0.45], [0.20, 0.60, 0.30], [0.60, 0.70, 1.00], [0.75, 0.65, 0.10], [0.45, 0.25, 0.65], [0.10, 0.55, 0.70],
+    [1.00, 0.70, 0.55], [0.40, 0.65, 0.15], [1.00, 0.65, 0.90], [0.60, 0.85, 0.80], [0.85, 0.75, 0.60], [0.75, 0.80, 1.00]], np.float32)
+
+MESH_COLOR_MODES = ('identity', 'same', 'track_id', 'part')
 
 
 def setup_renderer(name='sim3dr', **kwargs):
@@ -30,6 +54,12 @@ def mesh_color_left2right(trans, color_table=None):
     return np.array([table[i % len(table)] for i in inds])
 
 
+def mesh_color_trackID(track_ids, color_table=None):
+    """Colour = the table's row track id modulo its length (vis_utils.py:238-241): stable while a person keeps the id."""
+    table = tracking_color_list if color_table is None else color_table
+    return np.array([table[tid % len(table)] for tid in track_ids])
+
+
 # show_items drawn on the device, in the order rendering_romp_bev_results appends their panels
 DEVICE_ITEMS = ('mesh', 'mesh_bird_view', 'mesh_side_view')
 
@@ -41,15 +71,33 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
     (verts + cam_trans, z negated), rotated and fitted by view_weak_perspective, onto a white h x h canvas.
     As in the reference, the side view is fitted to the frame's (h, w), not to the h x h canvas it is drawn on:
     for a frame wider than high its centre lies at x = w / 2, right of the canvas centre (kept, not fixed).
+    `rendering_cfgs['mesh_color']`, for every panel: 'identity' colours persons left to right and 'same' alike, as the
+    reference's values do without tracking; [romp_amd] 'track_id' by `outputs['track_ids']` (mesh_color_trackID; what
+    the reference's 'identity' does once track ids exist), left to right when there are none; [romp_amd] 'part' paints
+    every vertex with part_palette[rendering_cfgs['part_labels']] (the (V,) labels of SMPL.part_labels) under white
+    ambient light.
     `keys`: an int64 device tensor of h*w words the 'mesh' panel rasterizes into, for `dense_maps(..., keys=keys)`."""
     triangles = outputs['smpl_face'].cpu().numpy().astype(np.int32)
     cam_trans = outputs['cam_trans']
-    if rendering_cfgs['mesh_color'] == 'identity':
+    mode = rendering_cfgs['mesh_color']
+    part_colors = None
+    if mode == 'identity' or (mode == 'track_id' and 'track_ids' not in outputs):
         mesh_colors = mesh_color_left2right(cam_trans)
-    elif rendering_cfgs['mesh_color'] == 'same':
+    elif mode == 'track_id':
+        track_ids = outputs['track_ids']
+        mesh_colors = mesh_color_trackID(track_ids.cpu().numpy() if torch.is_tensor(track_ids) else np.asarray(track_ids))
+        mesh_colors = mesh_colors.reshape(len(cam_trans), 3)
+    elif mode == 'same':
         mesh_colors = np.array([[.9, .9, .8] for _ in range(len(cam_trans))])
+    elif mode == 'part':
+        if rendering_cfgs.get('part_labels') is None:
+            raise ValueError("mesh_color 'part' needs rendering_cfgs['part_labels'], the (V,) part label of every vertex")
+        mesh_colors = np.ones((len(cam_trans), 3))
+        labels = rendering_cfgs['part_labels']
+        labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+        part_colors = part_palette[labels.reshape(-1).astype(np.int64)]                    # (V,3): the same for every person
     else:
-        raise ValueError(rendering_cfgs['mesh_color'])
+        raise ValueError(mode)
     items = rendering_cfgs['items']
     unsupported = [it for it in items if it not in DEVICE_ITEMS]
     if unsupported:
@@ -62,7 +110,8 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
     if 'mesh' in items:
         vertices = outputs['verts_camed_org'][depth_order.to(outputs['verts_camed_org'].device)].clone()
         vertices[:, :, 2] = vertices[:, :, 2] * -1
-        result_image.append(renderer(vertices, triangles, np.ascontiguousarray(image), mesh_colors=colors, keys=keys))
+        result_image.append(renderer(vertices, triangles, np.ascontiguousarray(image), mesh_colors=colors,
+                                     vert_colors=_per_person(part_colors, vertices), keys=keys))
     views = [(it, rx, ry, shape) for it, rx, ry, shape in (('mesh_bird_view', -90, 0, (h, h)), ('mesh_side_view', 0, -90, (h, w)))
              if it in items]
     if views:
@@ -72,9 +121,16 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
         background = torch.full((h, h, 3), 255, dtype=torch.uint8, device=verts_tran.device)
         for _, rx, ry, shape in views:
             view = view_weak_perspective(verts_tran, rx, ry, shape, expand_ratio=1.2)[0] if len(verts_tran) else verts_tran
-            result_image.append(renderer(view, triangles, background, mesh_colors=colors))
+            result_image.append(renderer(view, triangles, background, mesh_colors=colors, vert_colors=_per_person(part_colors, view)))
     outputs['rendered_image'] = np.concatenate(result_image, 1)
     return outputs
+
+
+def _per_person(part_colors, verts):
+    """part_colors (V,3) numpy -> (n,V,3) on the device of verts (n,V,3), or None."""
+    if part_colors is None:
+        return None
+    return torch.from_numpy(part_colors).to(verts.device).unsqueeze(0).expand(len(verts), -1, -1).contiguous()
 
 
 def mesh_panel_keys(image_shape, device):
