@@ -124,6 +124,9 @@ def load():
         'romp_preprocess_crops': (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(C.c_int32), vp, i32, C.POINTER(C.c_float), vp]),
         'romp_bev_crowd_merge': (C.c_int, [vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, C.c_double, f,
                                            vp, vp, vp, vp, vp, vp]),
+        'romp_eval_match2d': (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f, i32, vp, vp, vp, vp]),
+        'romp_eval_points': (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'romp_eval_accumulate': (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -152,6 +155,8 @@ VIEW_EXPORTS = ['romp_sim3dr_render_batch', 'romp_view_weak_perspective']
 MAP_EXPORTS = ['romp_sim3dr_maps']
 # include/romp_hip_views.h: per-vertex colours and the specular exponent
 TEXTURE_EXPORTS = ['romp_sim3dr_light_tex', 'romp_sim3dr_render_batch_tex']
+# include/romp_hip_eval.h: benchmark scoring (2-D matching, MPJPE / PA-MPJPE / PVE, the running accumulator)
+EVAL_EXPORTS = ['romp_eval_match2d', 'romp_eval_points', 'romp_eval_accumulate']
 
 
 def has_bf16x3():
