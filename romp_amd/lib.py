@@ -127,6 +127,8 @@ def load():
         'romp_eval_match2d': (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f, i32, vp, vp, vp, vp]),
         'romp_eval_points': (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         'romp_eval_accumulate': (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]),
+        'romp_rh_score': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, f, f, vp, vp, vp, vp]),
+        'romp_rh_accumulate': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -157,6 +159,8 @@ MAP_EXPORTS = ['romp_sim3dr_maps']
 TEXTURE_EXPORTS = ['romp_sim3dr_light_tex', 'romp_sim3dr_render_batch_tex']
 # include/romp_hip_eval.h: benchmark scoring (2-D matching, MPJPE / PA-MPJPE / PVE, the running accumulator)
 EVAL_EXPORTS = ['romp_eval_match2d', 'romp_eval_points', 'romp_eval_accumulate']
+# include/romp_hip_rh.h: the Relative Human benchmark (PCKh, depth-relation counts per age, the running accumulator)
+RH_EXPORTS = ['romp_rh_score', 'romp_rh_accumulate']
 
 
 def has_bf16x3():
