@@ -55,7 +55,9 @@ def bev_settings(input_args=sys.argv[1:]):
                    help='[romp_amd] off by default (the reference defaults to on, with --show_items mesh,mesh_bird_view)')
     p.add_argument('--renderer', type=str, default='sim3dr')
     p.add_argument('--show_items', type=str, default='mesh',
-                   help='any of mesh, mesh_bird_view, mesh_side_view (panels in that order); the cv2 overlays are not supported')
+                   help='any of mesh, mesh_bird_view, mesh_side_view (panels in that order) and rotate_mesh (a 96-frame turntable of '
+                        'the scene, returned as rotate_mesh_frames); the cv2 overlays are not supported')
+    p.add_argument('--rotate_size', type=int, default=512, help='[romp_amd] side of the square frames of --show_items rotate_mesh')
     p.add_argument('--mesh_color', type=str, default='identity', choices=['identity', 'same', 'track_id', 'part'],
                    help='[romp_amd] how --render_mesh colours the meshes: identity: per person, left to right (default); same: one colour; '
                         'track_id: per person by track id, stable across frames with -t; part: per vertex by SMPL body part')
@@ -437,7 +439,8 @@ class BEV(nn.Module):
         if self.settings.render_mesh:
             keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
             cfgs = {'mesh_color': getattr(self.settings, 'mesh_color', 'identity'), 'items': self.visualize_items,
-                    'renderer': getattr(self.settings, 'renderer', 'sim3dr'), 'part_labels': self.smpl_parser.smpl_model.part_labels}
+                    'renderer': getattr(self.settings, 'renderer', 'sim3dr'), 'part_labels': self.smpl_parser.smpl_model.part_labels,
+                    'rotate_size': getattr(self.settings, 'rotate_size', 512)}
             res = rendering_romp_bev_results(self.renderer, res, image, cfgs, keys=keys)
         if dense:
             res = dense_maps(self.renderer, res, image.shape, self.smpl_parser.smpl_model.part_labels, keys=keys)

@@ -41,7 +41,8 @@ def build(force=False, verbose=False, extra_flags=(), lib=None, objdir=None, wit
         with_bx3 = os.environ.get('ROMP_WITH_BX3', '0') not in ('', '0')
     sources = SOURCES + ([OPTIONAL_BX3] if with_bx3 else [])
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + \
-              [os.path.join(HERE, '..', 'include', h) for h in ('romp_hip.h', 'romp_hip_views.h', 'romp_hip_maps.h', 'romp_hip_eval.h', 'romp_hip_rh.h')]
+              [os.path.join(HERE, '..', 'include', h) for h in ('romp_hip.h', 'romp_hip_views.h', 'romp_hip_maps.h', 'romp_hip_eval.h', 'romp_hip_rh.h',
+                                                              'romp_hip_canvases.h')]
     objdir = objdir or os.path.join(HERE, 'build')
     lib = lib or LIB
     os.makedirs(objdir, exist_ok=True)

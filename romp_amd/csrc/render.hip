@@ -27,6 +27,7 @@
 #include "common.h"
 #include "../../include/romp_hip_views.h"
 #include "../../include/romp_hip_maps.h"
+#include "../../include/romp_hip_canvases.h"
 
 #pragma clang fp contract(off)
 
@@ -75,17 +76,20 @@ __device__ __forceinline__ float clip01(float x) { return fminf(fmaxf(x, 0.f), 1
 // the clipped light itself.  cfg.spec_exp = e: each component of v2v * reflection is raised to e before the three are
 // summed (renderer.py:110).  e = 1 multiplies nothing; e >= 2 is t * t * ... * t, e - 1 rounded multiplies from left to
 // right: numpy's square for e = 2, within rounding of its powf for e > 2 (not bit for bit).
+// rows: mesh m takes its ambient term and texture from row rows[m] (romp_sim3dr_render_canvases), or from row m for null.
 __global__ __launch_bounds__(1024) void sim3dr_light_kernel(const float* __restrict__ v, const float* __restrict__ nrm, int nver,
                                                              LightCfg cfg, const float* __restrict__ ambient,
-                                                             const float* __restrict__ texture, float* __restrict__ light) {
+                                                             const float* __restrict__ texture, const int32_t* __restrict__ rows,
+                                                             float* __restrict__ light) {
     __shared__ float red[3][1024];
     __shared__ float s_min[3], s_max1, s_max3[3];
     const int tid = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * nver * 3;
     v += base; nrm += base; light += base;
-    if (texture) texture += base;
-    const float amb[3] = {ambient ? ambient[3 * blockIdx.x] : cfg.ambient[0], ambient ? ambient[3 * blockIdx.x + 1] : cfg.ambient[1],
-                          ambient ? ambient[3 * blockIdx.x + 2] : cfg.ambient[2]};
+    const size_t row = rows ? (size_t)rows[blockIdx.x] : (size_t)blockIdx.x;
+    if (texture) texture += row * nver * 3;
+    const float amb[3] = {ambient ? ambient[3 * row] : cfg.ambient[0], ambient ? ambient[3 * row + 1] : cfg.ambient[1],
+                          ambient ? ambient[3 * row + 2] : cfg.ambient[2]};
     float m[3] = {3.4e38f, 3.4e38f, 3.4e38f};
     for (int i = tid; i < nver; i += 1024)
         for (int k = 0; k < 3; ++k) m[k] = fminf(m[k], v[3 * i + k]);
@@ -214,6 +218,19 @@ __global__ void sim3dr_raster_kernel(const float* __restrict__ v, const int32_t*
         raster_triangle(v + (size_t)mesh * nver * 3, tri, t, mesh, mbits, h, w, keys);
 }
 
+// rasterize_kernel.cpp:280-289: the colour of triangle t of one mesh (v, col: nver x 3 / nver x c) at pixel (x, y) -> px[0..c)
+__device__ __forceinline__ void paint_pixel(const float* __restrict__ v, const int32_t* __restrict__ tri, const float* __restrict__ col,
+                                            int t, int x, int y, int c, unsigned char* __restrict__ px) {
+    const int a = tri[3 * t], b = tri[3 * t + 1], cc = tri[3 * t + 2];
+    float w0, w1, w2;
+    point_weight((float)x, (float)y, v[3 * a], v[3 * a + 1], v[3 * b], v[3 * b + 1], v[3 * cc], v[3 * cc + 1], w0, w1, w2);
+    const float alpha = 1.f;
+    for (int k = 0; k < c; ++k) {
+        const float pc = w0 * col[c * a + k] + w1 * col[c * b + k] + w2 * col[c * cc + k];
+        px[k] = (unsigned char)((1 - alpha) * px[k] + alpha * 255 * pc);      // rasterize_kernel.cpp:287-288
+    }
+}
+
 // v: n x nver x 3, col: n x nver x c; the winning mesh and triangle come out of the key
 __global__ void sim3dr_resolve_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri, const float* __restrict__ col,
                                       const unsigned long long* __restrict__ keys, int nver, int mbits, int h, int w, int c,
@@ -225,18 +242,52 @@ __global__ void sim3dr_resolve_kernel(const float* __restrict__ v, const int32_t
     const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
     const int t = (int)(tmask - (key & tmask));
     const size_t mesh = mbits ? (size_t)(key >> (64 - mbits)) : 0;
-    v += mesh * nver * 3;
-    col += mesh * nver * c;
     const int x = i % w, y = i / w;
-    const int a = tri[3 * t], b = tri[3 * t + 1], cc = tri[3 * t + 2];
-    float w0, w1, w2;
-    point_weight((float)x, (float)y, v[3 * a], v[3 * a + 1], v[3 * b], v[3 * b + 1], v[3 * cc], v[3 * cc + 1], w0, w1, w2);
     const int row = reverse ? (h - 1 - y) : y;
-    const float alpha = 1.f;
-    for (int k = 0; k < c; ++k) {
-        const float pc = w0 * col[c * a + k] + w1 * col[c * b + k] + w2 * col[c * cc + k];
-        unsigned char* px = image + ((size_t)row * w + x) * c + k;
-        *px = (unsigned char)((1 - alpha) * (*px) + alpha * 255 * pc);      // rasterize_kernel.cpp:287-288
+    paint_pixel(v + mesh * nver * 3, tri, col + mesh * nver * c, t, x, y, c, image + ((size_t)row * w + x) * c);
+}
+
+// ---- many canvases in one pass (romp_hip_canvases.h) -------------------------------------------------------
+// Canvas c of C paints the slots [lo, lo + count) of v with a fresh z-buffer per slot: romp_sim3dr_render_batch on that
+// slice, the mesh index in the key counted from lo and mesh_bits(count) key bits for it.  The range is read from the
+// device offsets by every thread that needs it (two wave-uniform loads), clamped to [0, n]; a decreasing pair is empty.
+__device__ __forceinline__ void canvas_range(const int32_t* __restrict__ off, int c, int n, int& lo, int& count, int& mbits) {
+    lo = min(max(off[c], 0), n);
+    count = max(min(max(off[c + 1], 0), n) - lo, 0);
+    mbits = count <= 1 ? 0 : 32 - __clz(count - 1);                        // ceil(log2 count), mesh_bits() of the host
+}
+
+// grid.x: triangles, grid.z walks the canvases, grid.y the slots of a canvas (keys: C x h x w)
+__global__ void sim3dr_raster_canvases_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri, int ntri, int n, int nver,
+                                              const int32_t* __restrict__ off, int C, int h, int w,
+                                              unsigned long long* __restrict__ keys) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntri) return;
+    for (int c = blockIdx.z; c < C; c += gridDim.z) {
+        int lo, count, mbits;
+        canvas_range(off, c, n, lo, count, mbits);
+        for (int m = blockIdx.y; m < count; m += gridDim.y)
+            raster_triangle(v + (size_t)(lo + m) * nver * 3, tri, t, m, mbits, h, w, keys + (size_t)c * h * w);
+    }
+}
+
+// one thread per pixel of all canvases (image: C x h x w x 3, col: n x nver x 3): 64-bit pixel and byte indices
+__global__ __launch_bounds__(256) void sim3dr_resolve_canvases_kernel(const float* __restrict__ v, const int32_t* __restrict__ tri,
+                                                                      const float* __restrict__ col,
+                                                                      const unsigned long long* __restrict__ keys,
+                                                                      const int32_t* __restrict__ off, int C, int n, int nver, int h,
+                                                                      int w, unsigned char* __restrict__ image) {
+    const size_t hw = (size_t)h * w, total = hw * C;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const unsigned long long key = keys[i];
+        if (key == 0ull) continue;
+        const size_t c = i / hw, p = i - c * hw;
+        int lo, count, mbits;
+        canvas_range(off, (int)c, n, lo, count, mbits);
+        const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
+        const int t = (int)(tmask - (key & tmask));
+        const size_t mesh = (size_t)lo + (mbits ? (size_t)(key >> (64 - mbits)) : 0);
+        paint_pixel(v + mesh * nver * 3, tri, col + mesh * nver * 3, t, (int)(p % w), (int)(p / w), 3, image + i * 3);
     }
 }
 
@@ -382,6 +433,74 @@ __global__ __launch_bounds__(256) void view_apply_kernel(float* __restrict__ out
         }
 }
 
+// ---- turntable (romp_hip_canvases.h): K views of one scene with one shared fit -------------------------------
+constexpr int kTurnViews = 128;                                            // views per launch: their cos / sin travel as kernel arguments
+
+struct TurnCfg {
+    float cs[kTurnViews][4];   // cos, sin of the azimuth, cos, sin of the tilt: float32 of float64 cos / sin
+    float half[2];
+    float expand_ratio;
+};
+
+__global__ __launch_bounds__(256) void turntable_bounds_kernel(const float* __restrict__ v, long long count, unsigned* __restrict__ work) {
+    unsigned acc[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256)
+        for (int k = 0; k < 3; ++k) {
+            acc[k] = min(acc[k], orderable(v[3 * i + k]));
+            acc[3 + k] = min(acc[3 + k], ~orderable(v[3 * i + k]));
+        }
+    block_min_u32<6>(acc, work);
+}
+
+// Rx(tilt) . (Ry(azimuth) . a), two rounded steps with the full matrices (their 0 and 1 entries multiply too)
+__device__ __forceinline__ void turn_rotate(const float* cs, const float (&a)[3], float (&r)[3]) {
+    const float ry[9] = {cs[0], 0.f, cs[1], 0.f, 1.f, 0.f, -cs[1], 0.f, cs[0]};
+    const float rx[9] = {1.f, 0.f, 0.f, 0.f, cs[2], -cs[3], 0.f, cs[3], cs[2]};
+    float b[3];
+    rotate3(ry, a[0], a[1], a[2], b[0], b[1], b[2]);
+    rotate3(rx, b[0], b[1], b[2], r[0], r[1], r[2]);
+}
+
+// grid.y: the views of this launch; work[6] gathers the extent of all of them
+__global__ __launch_bounds__(256) void turntable_extent_kernel(const float* __restrict__ v, long long count, TurnCfg cfg,
+                                                               unsigned* __restrict__ work) {
+    float c[3];
+    view_center(work, c);
+    const float cs[4] = {cfg.cs[blockIdx.y][0], cfg.cs[blockIdx.y][1], cfg.cs[blockIdx.y][2], cfg.cs[blockIdx.y][3]};
+    unsigned acc[1] = {~0u};
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const float a[3] = {v[3 * i] - c[0], v[3 * i + 1] - c[1], v[3 * i + 2] - c[2]};
+        float r[3];
+        turn_rotate(cs, a, r);
+        for (int k = 0; k < 2; ++k) acc[0] = min(acc[0], ~__float_as_uint(fabsf(r[k] / cfg.half[k])));
+    }
+    block_min_u32<1>(acc, work + 6);
+}
+
+// grid.y: the views k0 + blockIdx.y; out (K,n,nver,3); order (K,n): the mesh in slot j of view k (clamped to [0, n)), or null
+__global__ __launch_bounds__(256) void turntable_apply_kernel(const float* __restrict__ v, int n, int nver, TurnCfg cfg, int k0,
+                                                              const int32_t* __restrict__ order, const unsigned* __restrict__ work,
+                                                              float* __restrict__ out, float* __restrict__ center_scale) {
+    float c[3];
+    view_center(work, c);
+    const float scale = 1.f / (cfg.expand_ratio * __uint_as_float(~work[6]));
+    if (k0 == 0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 4) center_scale[threadIdx.x] = threadIdx.x < 3 ? c[threadIdx.x] : scale;
+    const float cs[4] = {cfg.cs[blockIdx.y][0], cfg.cs[blockIdx.y][1], cfg.cs[blockIdx.y][2], cfg.cs[blockIdx.y][3]};
+    const long long count = (long long)n * nver, k = k0 + (long long)blockIdx.y;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        const long long j = i / nver, p = i - j * nver;
+        const long long src = order ? (long long)min(max(order[k * n + j], 0), n - 1) : j;
+        const float* s = v + (src * nver + p) * 3;
+        const float a[3] = {s[0] - c[0], s[1] - c[1], s[2] - c[2]};
+        float r[3];
+        turn_rotate(cs, a, r);
+        float* o = out + (k * count + i) * 3;
+        o[0] = r[0] * scale + cfg.half[0];
+        o[1] = r[1] * scale + cfg.half[1];
+        o[2] = r[2] * scale;
+    }
+}
+
 }  // namespace romp
 
 using namespace romp;
@@ -420,7 +539,7 @@ int render_batch(const char* who, unsigned char* image, int h, int w, const floa
     hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256, gy), dim3(256), 0, st, verts, tris, adj_off, adj_ent, nver, n,
                        normals);
     hipLaunchKernelGGL(sim3dr_light_kernel, dim3(n), dim3(1024), 0, st, verts, normals, nver, light_cfg(cfg_host, spec_exp), ambient,
-                       textures, light);
+                       textures, (const int32_t*)nullptr, light);
     ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, (size_t)h * w * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(sim3dr_raster_kernel, dim3((ntri + 63) / 64, gy), dim3(64), 0, st, verts, tris, ntri, n, nver, mbits, h, w,
                        keys);
@@ -446,7 +565,7 @@ int romp_sim3dr_normals(const float* verts, const int32_t* tris, const int32_t* 
 int romp_sim3dr_light(const float* verts, const float* normals, int nver, const float* cfg_host, float* light, void* stream) {
     ROMP_REQUIRE(verts && normals && cfg_host && light && nver > 0, "romp_sim3dr_light: bad arguments");
     hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver, light_cfg(cfg_host),
-                       (const float*)nullptr, (const float*)nullptr, light);
+                       (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, light);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -456,7 +575,7 @@ int romp_sim3dr_light_tex(const float* verts, const float* normals, int nver, co
     ROMP_REQUIRE(verts && normals && cfg_host && light && nver > 0, "romp_sim3dr_light_tex: bad arguments");
     ROMP_REQUIRE(specular_exp >= 1, "romp_sim3dr_light_tex: specular_exp must be an integer >= 1, got %d", specular_exp);
     hipLaunchKernelGGL(sim3dr_light_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, verts, normals, nver,
-                       light_cfg(cfg_host, specular_exp), (const float*)nullptr, texture, light);
+                       light_cfg(cfg_host, specular_exp), (const float*)nullptr, texture, (const int32_t*)nullptr, light);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -508,6 +627,66 @@ int romp_view_weak_perspective(const float* verts, int n, int nver, double rx, d
     hipLaunchKernelGGL(view_rotate_kernel, dim3(grid), dim3(256), 0, st, verts, count, cfg, out, work);
     hipLaunchKernelGGL(view_extent_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, work);
     hipLaunchKernelGGL(view_apply_kernel, dim3(grid), dim3(256), 0, st, out, count, cfg, (const unsigned*)work, center_scale);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_sim3dr_render_canvases(unsigned char* images, int C, int h, int w, const float* verts, int n, int nver,
+                                const int32_t* canvas_off, const int32_t* tris, int ntri, const int32_t* adj_off,
+                                const int32_t* adj_ent, const float* ambient, const float* cfg_host, const float* textures,
+                                const int32_t* rows, int specular_exp, float* normals, float* light, unsigned long long* keys,
+                                void* stream) {
+    ROMP_REQUIRE(images && verts && canvas_off && tris && adj_off && adj_ent && ambient && cfg_host && normals && light && keys &&
+                 C > 0 && n > 0 && nver > 0 && ntri > 0 && h > 0 && w > 0, "romp_sim3dr_render_canvases: bad arguments");
+    ROMP_REQUIRE(specular_exp >= 1, "romp_sim3dr_render_canvases: specular_exp must be an integer >= 1, got %d", specular_exp);
+    const int mbits = mesh_bits(n);                                          // of all slots: no canvas holds more
+    ROMP_REQUIRE((long long)ntri <= (1ll << (32 - mbits)),
+                 "romp_sim3dr_render_canvases: %d meshes leave %d key bits for the triangle index, %d triangles do not fit", n,
+                 32 - mbits, ntri);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t pixels = (size_t)C * h * w;
+    hipLaunchKernelGGL(sim3dr_normal_kernel, dim3((nver + 255) / 256, (unsigned)std::min(n, kMaxGridY)), dim3(256), 0, st, verts, tris,
+                       adj_off, adj_ent, nver, n, normals);
+    hipLaunchKernelGGL(sim3dr_light_kernel, dim3(n), dim3(1024), 0, st, verts, normals, nver, light_cfg(cfg_host, specular_exp), ambient,
+                       textures, rows, light);
+    ROMP_HIP_CHECK(hipMemsetAsync(keys, 0, pixels * sizeof(unsigned long long), st));
+    const unsigned gy = (unsigned)std::min((n + C - 1) / C, kMaxGridY);     // an even split fills it; a fuller canvas strides
+    hipLaunchKernelGGL(sim3dr_raster_canvases_kernel, dim3((ntri + 63) / 64, gy, (unsigned)std::min(C, kMaxGridY)), dim3(64), 0, st,
+                       verts, tris, ntri, n, nver, canvas_off, C, h, w, keys);
+    const unsigned gx = (unsigned)std::min<size_t>((pixels + 255) / 256, 1u << 22);
+    hipLaunchKernelGGL(sim3dr_resolve_canvases_kernel, dim3(gx), dim3(256), 0, st, verts, tris, light,
+                       (const unsigned long long*)keys, canvas_off, C, n, nver, h, w, images);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
+}
+
+int romp_view_turntable(const float* verts, int n, int nver, int K, const double* azimuth_deg, const double* tilt_deg,
+                        const int32_t* order, int img_h, int img_w, double expand_ratio, float* out, float* center_scale,
+                        unsigned* work, void* stream) {
+    ROMP_REQUIRE(verts && azimuth_deg && tilt_deg && out && center_scale && work && n > 0 && nver > 0 && K > 0 && img_h > 0 &&
+                 img_w > 0 && expand_ratio > 0, "romp_view_turntable: bad arguments");
+    TurnCfg cfg;
+    cfg.half[0] = (float)(img_w / 2.0); cfg.half[1] = (float)(img_h / 2.0);
+    cfg.expand_ratio = (float)expand_ratio;
+    const long long count = (long long)n * nver;
+    const unsigned grid = (unsigned)std::min<long long>((count + 255) / 256, 1024);
+    hipStream_t st = (hipStream_t)stream;
+    ROMP_HIP_CHECK(hipMemsetAsync(work, 0xFF, 7 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(turntable_bounds_kernel, dim3(grid), dim3(256), 0, st, verts, count, work);
+    for (int pass = 0; pass < 2; ++pass)                                     // every view's extent before any view is scaled
+        for (int k0 = 0; k0 < K; k0 += kTurnViews) {
+            const int kc = std::min(K - k0, kTurnViews);
+            for (int k = 0; k < kc; ++k) {
+                const double az = azimuth_deg[k0 + k] * (M_PI / 180.0), ti = tilt_deg[k0 + k] * (M_PI / 180.0);   // np.radians
+                cfg.cs[k][0] = (float)std::cos(az); cfg.cs[k][1] = (float)std::sin(az);
+                cfg.cs[k][2] = (float)std::cos(ti); cfg.cs[k][3] = (float)std::sin(ti);
+            }
+            if (pass == 0)
+                hipLaunchKernelGGL(turntable_extent_kernel, dim3(grid, kc), dim3(256), 0, st, verts, count, cfg, work);
+            else
+                hipLaunchKernelGGL(turntable_apply_kernel, dim3(grid, kc), dim3(256), 0, st, verts, n, nver, cfg, k0, order,
+                                   (const unsigned*)work, out, center_scale);
+        }
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

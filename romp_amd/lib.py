@@ -129,6 +129,10 @@ def load():
         'romp_eval_accumulate': (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]),
         'romp_rh_score': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, f, f, vp, vp, vp, vp]),
         'romp_rh_accumulate': (C.c_int, [vp, i32, vp, i32, vp, i32, vp, vp]),
+        'romp_sim3dr_render_canvases': (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_float), vp, vp,
+                                                  i32, vp, vp, vp, vp]),
+        'romp_view_turntable': (C.c_int, [vp, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, i32, i32, C.c_double,
+                                          vp, vp, vp, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -161,6 +165,8 @@ TEXTURE_EXPORTS = ['romp_sim3dr_light_tex', 'romp_sim3dr_render_batch_tex']
 EVAL_EXPORTS = ['romp_eval_match2d', 'romp_eval_points', 'romp_eval_accumulate']
 # include/romp_hip_rh.h: the Relative Human benchmark (PCKh, depth-relation counts per age, the running accumulator)
 RH_EXPORTS = ['romp_rh_score', 'romp_rh_accumulate']
+# include/romp_hip_canvases.h: many canvases in one pass (frame batches, the mesh turntable)
+CANVAS_EXPORTS = ['romp_sim3dr_render_canvases', 'romp_view_turntable']
 
 
 def has_bf16x3():

@@ -43,7 +43,10 @@ def romp_settings(input_args=sys.argv[1:]):
     parser.add_argument('--renderer', type=str, default='sim3dr', help='Choose the renderer for visualizaiton')
     parser.add_argument('--show', action='store_true', help='Whether to show the rendered results')
     parser.add_argument('--show_items', type=str, default='mesh',
-                        help='The items to visualized: any of mesh, mesh_bird_view, mesh_side_view (panels in that order)')
+                        help='The items to visualized: any of mesh, mesh_bird_view, mesh_side_view (panels in that order) and '
+                             'rotate_mesh (a 96-frame turntable of the scene, returned as rotate_mesh_frames)')
+    parser.add_argument('--rotate_size', type=int, default=512,
+                        help='[romp_amd] side of the square frames of --show_items rotate_mesh')
     parser.add_argument('--mesh_color', type=str, default='identity', choices=list(MESH_COLOR_MODES),
                         help='[romp_amd] how --render_mesh colours the meshes: identity: per person, left to right (default); same: one colour; '
                              'track_id: per person by track id, stable across frames with -t (left to right without track ids); '
@@ -302,7 +305,8 @@ class ROMP(nn.Module):
         keys = None
         if self.settings.render_mesh:                                                       # main.py:170-172
             rendering_cfgs = {'mesh_color': getattr(self.settings, 'mesh_color', 'identity'), 'items': self.visualize_items,
-                              'renderer': self.settings.renderer, 'part_labels': self.smpl_parser.smpl_model.part_labels}
+                              'renderer': self.settings.renderer, 'part_labels': self.smpl_parser.smpl_model.part_labels,
+                              'rotate_size': getattr(self.settings, 'rotate_size', 512)}
             keys = mesh_panel_keys(image.shape, self.tdevice) if dense and 'mesh' in self.visualize_items else None
             outputs = rendering_romp_bev_results(self.renderer, outputs, image, rendering_cfgs, keys=keys)
         if dense:                                                                           # the mesh panel's raster pass serves both

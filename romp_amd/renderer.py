@@ -132,6 +132,9 @@ class Sim3DR(object):
         self.light_pos = convert_type(kwargs.get('light_pos', (0, 0, -5)))
         self.view_pos = convert_type(kwargs.get('view_pos', (0, 0, 5)))
         self.device = kwargs.get('device', None)
+        self.max_canvases = int(kwargs.get('max_canvases', 32))            # [romp_amd] canvases per render_canvases launch set
+        if self.max_canvases < 1:
+            raise ValueError('max_canvases must be >= 1, got %d' % self.max_canvases)
         e = self.specular_exp
         if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < 1:
             raise NotImplementedError('specular_exp must be an integer >= 1 on the device path (it multiplies repeatedly; '
@@ -246,6 +249,109 @@ class Sim3DR(object):
                                    keys, None if vert_colors is None else vert_colors[ind:ind + 1])
         return img.cpu().numpy()
 
+    def render_canvases(self, verts, triangles, canvases, offsets, mesh_colors=np.array([[1, 0.6, 0.4]]), vert_colors=None, rows=None,
+                        keys=None, return_tensor=False):
+        """[romp_amd] `__call__` for C canvases of one size at once (romp_sim3dr_render_canvases, include/romp_hip_canvases.h):
+        the slots offsets[c] .. offsets[c+1]-1 of verts (n,V,3) (ONE topology `triangles`) are painted in slot order onto a copy
+        of canvases[c], what `__call__(verts[slice], triangles, canvases[c], ...)` paints, byte for byte, in five launches
+        whatever C and n are, and all canvases come back in one download.
+        `canvases`: (C,h,w,3) uint8, numpy or a device tensor, or one (h,w,3) canvas for all C = len(offsets) - 1; not modified.
+        `offsets`: (C+1,) ascending, an array (host) or an int32 device tensor such as `evaluation.batch_offsets(batch_ids, B)`
+        (no host sync then).  The device clamps each offset to [0, n]; a decreasing pair is an empty canvas, which keeps its bytes.
+        Colours: without `rows`, slot j is lit with mesh_colors[j % len(mesh_colors)] and painted with vert_colors[j]
+        ((n,V,3) or None), as in `__call__` on all n slots; with `rows` (n,) ints, slot j takes row rows[j] of mesh_colors (R,3)
+        and of vert_colors (R,V,3): a person who sits in a different slot on every canvas keeps one row.
+        `keys`: a contiguous int64 device tensor of C*h*w words to rasterize into; keys[c] then holds what `__call__` leaves for
+        canvas c's slice (for `maps(verts[slice], ..., keys=keys[c])`).
+        More than `max_canvases` canvases (constructor, default 32) are rendered in chunks of that many so that the key scratch
+        stays bounded: host offsets let a chunk take its own slots only; with device offsets every chunk lights all n slots.
+        Returns (C,h,w,3) uint8: numpy, or the device tensor with return_tensor=True."""
+        dev = _device(self.device)
+        off_dev = off_host = None
+        if torch.is_tensor(offsets) and offsets.is_cuda:
+            off_dev = offsets.to(dev, torch.int32).contiguous().reshape(-1)
+            ncan = off_dev.numel() - 1
+        else:
+            off_host = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets).astype(np.int64).reshape(-1)
+            ncan = len(off_host) - 1
+        if ncan < 0:
+            raise ValueError('offsets must hold C + 1 values, got none')
+        if torch.is_tensor(canvases):
+            img = canvases.to(dev, torch.uint8)
+        else:
+            img = torch.from_numpy(np.ascontiguousarray(canvases)).to(dev)
+        if img.dim() == 3:
+            img = img.unsqueeze(0).expand(ncan, -1, -1, -1)
+        if img.dim() != 4 or img.shape[3] != 3 or img.shape[0] != ncan:
+            raise ValueError('render_canvases paints %d canvases (C, h, w, 3), got %s' % (ncan, tuple(img.shape)))
+        img = img.clone(memory_format=torch.contiguous_format)             # a copy: the input is not modified
+        h, w = int(img.shape[1]), int(img.shape[2])
+        verts_dev = _verts_dev(verts, dev)
+        n = len(verts_dev)
+        if n and (verts_dev.dim() != 3 or verts_dev.shape[2] != 3):
+            raise ValueError('render_canvases takes (n, V, 3) vertices, got %s' % (tuple(verts_dev.shape),))
+        if n and len(np.shape(triangles)) != 2:
+            raise ValueError('render_canvases needs one triangle table (ntri, 3) for all meshes, got a list of topologies')
+        if keys is not None and not (torch.is_tensor(keys) and keys.dtype == torch.int64 and keys.device == dev and keys.is_contiguous()
+                                     and keys.numel() == ncan * h * w):
+            raise ValueError('keys must be a contiguous int64 tensor of %d x %d x %d words on %s' % (ncan, h, w, dev))
+        palette = np.asarray(mesh_colors).reshape(-1, 3)                   # (dtype kept: `_ambient` rounds as `__call__` does)
+        if rows is None:
+            nrow = n
+            colors = palette[np.arange(n) % len(palette)]
+        else:
+            nrow = len(palette)
+            colors = palette
+            if not torch.is_tensor(rows):
+                r = np.asarray(rows).reshape(-1)
+                if len(r) != n or (n and (r.min() < 0 or r.max() >= nrow)):
+                    raise ValueError('rows must hold %d indices into the %d rows of mesh_colors' % (n, nrow))
+            rows = _dev_array(rows, torch.int32, dev).reshape(-1)
+            if rows.numel() != n:
+                raise ValueError('rows must hold %d indices, got %d' % (n, rows.numel()))
+            rows = rows.clamp(0, max(nrow - 1, 0))                          # a device tensor is not read back: clamped instead
+        if vert_colors is not None:
+            vert_colors = _dev_array(vert_colors, torch.float32, dev)
+            if vert_colors.dim() != 3 or vert_colors.shape[0] != nrow or (n and tuple(vert_colors.shape[1:]) != tuple(verts_dev.shape[1:])):
+                raise ValueError('vert_colors must be (%d, V, 3) like the vertices %s, got %s'
+                                 % (nrow, tuple(verts_dev.shape), tuple(vert_colors.shape)))
+        if keys is not None and (n == 0 or ncan == 0):
+            keys.zero_()
+        if n == 0 or ncan == 0:
+            return img if return_tensor else img.cpu().numpy()
+        topo = _topology(triangles, verts_dev.shape[1], dev)
+        amb = torch.from_numpy(self._ambient(colors)).pin_memory().to(dev, non_blocking=True)   # no stream sync
+        if off_dev is None:
+            off_host = np.clip(off_host, 0, n)
+            off_dev = torch.from_numpy(off_host.astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+        step = self.max_canvases
+        scratch = keys.view(ncan, h * w) if keys is not None else torch.empty((min(ncan, step), h * w), dtype=torch.int64, device=dev)
+        lib = L.load()
+        cfg = self._light_cfg(colors[:1])
+        with torch.cuda.device(dev):
+            for c0 in range(0, ncan, step):
+                c1 = min(c0 + step, ncan)
+                lo, hi, off = 0, n, off_dev[c0:c1 + 1]
+                if off_host is not None and ncan > step:                    # this chunk's slots only
+                    lo, hi = int(off_host[c0:c1 + 1].min()), int(off_host[c0:c1 + 1].max())
+                    if hi <= lo:
+                        if keys is not None:
+                            scratch[c0:c1].zero_()
+                        continue
+                    off = torch.from_numpy((off_host[c0:c1 + 1] - lo).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
+                v = verts_dev[lo:hi]
+                normals, light = torch.empty_like(v), torch.empty_like(v)
+                if rows is None:
+                    a, tex, rw = amb[lo:hi], (None if vert_colors is None else vert_colors[lo:hi]), None
+                else:
+                    a, tex, rw = amb, vert_colors, rows[lo:hi]
+                k = scratch[c0:c1] if keys is not None else scratch[:c1 - c0]
+                L.check(lib.romp_sim3dr_render_canvases(L.ptr(img[c0:c1]), c1 - c0, h, w, L.ptr(v), hi - lo, topo.nver, L.ptr(off),
+                                                        L.ptr(topo.tri), topo.ntri, L.ptr(topo.adj_off), L.ptr(topo.adj_ent), L.ptr(a),
+                                                        cfg, L.ptr(tex), L.ptr(rw), self.specular_exp, L.ptr(normals), L.ptr(light),
+                                                        L.ptr(k), L.stream_ptr(dev)))
+        return img if return_tensor else img.cpu().numpy()
+
     MAPS = ('person_map', 'tri_map', 'bary_map', 'attr_map', 'label_map', 'vert_visible', 'person_pixels')
 
     def maps(self, verts_list, triangles, image_shape, mesh_ids=None, attrs=None, attr_bg=0., vert_labels=None, want=None, keys=None):
@@ -327,4 +433,35 @@ def view_weak_perspective(verts, rx, ry, img_shape, expand_ratio=1.2):
     with torch.cuda.device(dev):
         L.check(L.load().romp_view_weak_perspective(L.ptr(v), v.shape[0], v.shape[1], float(rx), float(ry), int(h), int(w),
                                                     float(expand_ratio), L.ptr(out), L.ptr(center_scale), L.ptr(work), L.stream_ptr(dev)))
+    return out, center_scale[:3], center_scale[3]
+
+
+def turntable_views(verts, azimuths, tilts, img_shape, expand_ratio=1.2, order=None):
+    """[romp_amd] K views of one scene for a turntable (romp_view_turntable, include/romp_hip_canvases.h), no host sync: verts
+    (n,V,3) device tensor, centred on its bbox centre c0, spun by azimuths[k] degrees about the vertical axis and THEN tilted by
+    tilts[k] degrees about the horizontal one (a number: the same tilt for every view), scaled by ONE scale for all views so that
+    the largest |xy| / (w/2, h/2) of any view is 1 / expand_ratio, and shifted to the centre of the img_shape = (h, w) canvas.
+    `order` (K,n) ints: slot j of view k holds mesh order[k, j] (the painter's order of that view); None: the mesh index.
+    -> (views (K,n,V,3), c0 (3,), scale ()) float32 device tensors."""
+    v = verts.float().contiguous()
+    dev = v.device
+    h, w = img_shape
+    az = np.ascontiguousarray(np.asarray(azimuths, np.float64).reshape(-1))
+    K = len(az)
+    if v.dim() != 3 or v.shape[2] != 3 or v.shape[0] < 1 or v.shape[1] < 1 or K < 1:
+        raise ValueError('turntable_views takes (n, V, 3) vertices and K >= 1 angles, got %s and %d' % (tuple(v.shape), K))
+    ti = np.ascontiguousarray(np.broadcast_to(np.asarray(tilts, np.float64).reshape(-1), (K,)))
+    n, nver = int(v.shape[0]), int(v.shape[1])
+    if order is not None:
+        order = _dev_array(order, torch.int32, dev)
+        if tuple(order.shape) != (K, n):
+            raise ValueError('order must be (%d, %d), got %s' % (K, n, tuple(order.shape)))
+    out = torch.empty((K, n, nver, 3), dtype=torch.float32, device=dev)
+    center_scale = torch.empty(4, dtype=torch.float32, device=dev)
+    work = torch.empty(7, dtype=torch.int32, device=dev)
+    dp = C.POINTER(C.c_double)
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_view_turntable(L.ptr(v), n, nver, K, az.ctypes.data_as(dp), ti.ctypes.data_as(dp), L.ptr(order), int(h),
+                                             int(w), float(expand_ratio), L.ptr(out), L.ptr(center_scale), L.ptr(work),
+                                             L.stream_ptr(dev)))
     return out, center_scale[:3], center_scale[3]

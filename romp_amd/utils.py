@@ -80,7 +80,8 @@ def img_preprocess_device(image, device, input_size=512):
 
 def convert_tensor2numpy(outputs, del_keys=('verts_camed', 'smpl_face', 'pj2d', 'verts_camed_org')):
     """utils.py:32-41.  The device tensors of one dtype travel in ONE device-to-host copy (a dozen small `.cpu()` calls cost
-    more than the single-image network's post-processing); the arrays returned are views of that host block."""
+    more than the single-image network's post-processing); the arrays returned are views of that host block.  What is numpy
+    already ('rendered_image', the 'rotate_mesh_frames' of --show_items rotate_mesh) passes through untouched."""
     for key in del_keys:
         if key in outputs:
             del outputs[key]
@@ -135,6 +136,8 @@ class ResultSaver:
                 cv2.imwrite(save_path, outputs.pop('rendered_image'))
             except ImportError:
                 outputs.pop('rendered_image')
+        if outputs is not None and 'rotate_mesh_frames' in outputs:          # [romp_amd] --show_items rotate_mesh: (K,s,s,3) uint8
+            np.save(osp.splitext(save_path)[0] + '_rotate.npy', outputs.pop('rotate_mesh_frames'))
         if self.save_npz and outputs is not None:
             np.savez(osp.splitext(save_path)[0] + '.npz', results=outputs)
         if self.mode == 'video':

@@ -1,12 +1,12 @@
 """Mesh visualisation glue -- mirror of ``simple_romp/vis_human/main.py`` for the Sim3DR renderer
 (``setup_renderer`` :11-21, ``rendering_romp_bev_results`` :23-113, items 'mesh', 'mesh_bird_view',
-'mesh_side_view') and of ``vis_utils.mesh_color_left2right`` (:147-153) and ``mesh_color_trackID`` (:238-241).  The view transform and the
+'mesh_side_view', 'rotate_mesh'), of ``vis_utils.rendering_mesh_rotating_view`` (:101-125, the turntable) and of ``vis_utils.mesh_color_left2right`` (:147-153) and ``mesh_color_trackID`` (:238-241).  The view transform and the
 rasterization run on the device (renderer.py here); pyrender / open3d back-ends and the cv2 overlays
 (pj2d, j3d, center_conf, tracking) are not part of the MI355X path."""
 import numpy as np
 import torch
 
-from .renderer import Sim3DR, view_weak_perspective
+from .renderer import Sim3DR, turntable_views, view_weak_perspective
 
 # vis_utils.py:128-141 -- the palette persons are coloured with, left to right in the image
 color_table_default = np.array([
@@ -60,8 +60,30 @@ def mesh_color_trackID(track_ids, color_table=None):
     return np.array([table[tid % len(table)] for tid in track_ids])
 
 
-# show_items drawn on the device, in the order rendering_romp_bev_results appends their panels
-DEVICE_ITEMS = ('mesh', 'mesh_bird_view', 'mesh_side_view')
+# show_items drawn on the device, in the order rendering_romp_bev_results appends their panels ('rotate_mesh' is no panel:
+# its frames go to outputs['rotate_mesh_frames'])
+DEVICE_ITEMS = ('mesh', 'mesh_bird_view', 'mesh_side_view', 'rotate_mesh')
+
+
+def _mesh_colors(mode, cam_trans, track_ids=None, part_labels=None):
+    """(mesh_colors (n,3), part_colors (V,3) or None) of one frame's persons for a `mesh_color` mode."""
+    part_colors = None
+    if mode == 'identity' or (mode == 'track_id' and track_ids is None):
+        mesh_colors = mesh_color_left2right(cam_trans)
+    elif mode == 'track_id':
+        mesh_colors = mesh_color_trackID(track_ids.cpu().numpy() if torch.is_tensor(track_ids) else np.asarray(track_ids))
+        mesh_colors = mesh_colors.reshape(len(cam_trans), 3)
+    elif mode == 'same':
+        mesh_colors = np.array([[.9, .9, .8] for _ in range(len(cam_trans))])
+    elif mode == 'part':
+        if part_labels is None:
+            raise ValueError("mesh_color 'part' needs rendering_cfgs['part_labels'], the (V,) part label of every vertex")
+        mesh_colors = np.ones((len(cam_trans), 3))
+        labels = part_labels.cpu().numpy() if torch.is_tensor(part_labels) else np.asarray(part_labels)
+        part_colors = part_palette[labels.reshape(-1).astype(np.int64)]                    # (V,3): the same for every person
+    else:
+        raise ValueError(mode)
+    return mesh_colors, part_colors
 
 
 def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1, keys=None):
@@ -76,28 +98,14 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
     the reference's 'identity' does once track ids exist), left to right when there are none; [romp_amd] 'part' paints
     every vertex with part_palette[rendering_cfgs['part_labels']] (the (V,) labels of SMPL.part_labels) under white
     ambient light.
+    [romp_amd] 'rotate_mesh' (advertised by the reference's --show_items, drawn there by pyrender only): no panel; the
+    turntable of the scene, `rendering_mesh_rotating_view` of the meshes in camera space onto white s x s canvases,
+    s = rendering_cfgs.get('rotate_size', 512), as outputs['rotate_mesh_frames'] (K,s,s,3) uint8, K = 96 frames.
     `keys`: an int64 device tensor of h*w words the 'mesh' panel rasterizes into, for `dense_maps(..., keys=keys)`."""
     triangles = outputs['smpl_face'].cpu().numpy().astype(np.int32)
     cam_trans = outputs['cam_trans']
-    mode = rendering_cfgs['mesh_color']
-    part_colors = None
-    if mode == 'identity' or (mode == 'track_id' and 'track_ids' not in outputs):
-        mesh_colors = mesh_color_left2right(cam_trans)
-    elif mode == 'track_id':
-        track_ids = outputs['track_ids']
-        mesh_colors = mesh_color_trackID(track_ids.cpu().numpy() if torch.is_tensor(track_ids) else np.asarray(track_ids))
-        mesh_colors = mesh_colors.reshape(len(cam_trans), 3)
-    elif mode == 'same':
-        mesh_colors = np.array([[.9, .9, .8] for _ in range(len(cam_trans))])
-    elif mode == 'part':
-        if rendering_cfgs.get('part_labels') is None:
-            raise ValueError("mesh_color 'part' needs rendering_cfgs['part_labels'], the (V,) part label of every vertex")
-        mesh_colors = np.ones((len(cam_trans), 3))
-        labels = rendering_cfgs['part_labels']
-        labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-        part_colors = part_palette[labels.reshape(-1).astype(np.int64)]                    # (V,3): the same for every person
-    else:
-        raise ValueError(mode)
+    mesh_colors, part_colors = _mesh_colors(rendering_cfgs['mesh_color'], cam_trans, outputs.get('track_ids'),
+                                            rendering_cfgs.get('part_labels'))
     items = rendering_cfgs['items']
     unsupported = [it for it in items if it not in DEVICE_ITEMS]
     if unsupported:
@@ -114,7 +122,7 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
                                      vert_colors=_per_person(part_colors, vertices), keys=keys))
     views = [(it, rx, ry, shape) for it, rx, ry, shape in (('mesh_bird_view', -90, 0, (h, h)), ('mesh_side_view', 0, -90, (h, w)))
              if it in items]
-    if views:
+    if views or 'rotate_mesh' in items:
         verts = outputs['verts']
         verts_tran = (verts + cam_trans.to(verts.device).unsqueeze(1))[depth_order.to(verts.device)].float()
         verts_tran[:, :, 2] = verts_tran[:, :, 2] * -1
@@ -122,8 +130,79 @@ def rendering_romp_bev_results(renderer, outputs, image, rendering_cfgs, alpha=1
         for _, rx, ry, shape in views:
             view = view_weak_perspective(verts_tran, rx, ry, shape, expand_ratio=1.2)[0] if len(verts_tran) else verts_tran
             result_image.append(renderer(view, triangles, background, mesh_colors=colors, vert_colors=_per_person(part_colors, view)))
+        if 'rotate_mesh' in items:
+            size = int(rendering_cfgs.get('rotate_size', 512))
+            outputs['rotate_mesh_frames'] = rendering_mesh_rotating_view(renderer, verts_tran, triangles, (size, size), colors,
+                                                                         vert_colors=_per_person(part_colors, verts_tran))
     outputs['rendered_image'] = np.concatenate(result_image, 1)
     return outputs
+
+
+def turntable_angles(pause=24, step=5):
+    """vis_utils.py:101-110: the azimuths of the reference's rotating view in degrees: `pause` frames at 0, then the running sum
+    of 4 * (90 // step) steps of `step` degrees -- 96 frames by default, the last one at 360."""
+    return np.concatenate([np.zeros(pause), np.cumsum(np.ones(4 * (90 // step)) * step)])
+
+
+def rendering_mesh_rotating_view(renderer, verts_tran, triangles, canvas_hw, mesh_colors, vert_colors=None, azimuths=None, tilt=-20.):
+    """[romp_amd] vis_utils.rendering_mesh_rotating_view (:101-125, pyrender only there) on the device: the turntable of the
+    scene verts_tran (n,V,3) (device tensor, camera space with z negated as for the bird view: greater z is nearer) on white
+    canvas_hw = (h, w) canvases -> (K,h,w,3) uint8 numpy, one frame per azimuth (default `turntable_angles()`: 96 frames).
+    Every view spins the scene about its bbox centre by the azimuth, tilts it by `tilt` degrees (-20 looks down on the scene the
+    way the reference's camera, raised by 20 degrees, does) and uses ONE scale (`turntable_views`), so the scene does not
+    breathe while it turns.  Per view the persons are painted far to near: slots ascending by the z of the person's rotated
+    centroid, the lower index first on ties.  Person i keeps mesh_colors[i % len(mesh_colors)] and vert_colors[i] ((n,V,3) or
+    None) in every view.  One view transform and one `render_canvases` call: the launches do not grow with K or n, and all
+    frames come back in one download."""
+    h, w = int(canvas_hw[0]), int(canvas_hw[1])
+    az = turntable_angles() if azimuths is None else np.asarray(azimuths, np.float64).reshape(-1)
+    K, n = len(az), len(verts_tran)
+    white = np.full((h, w, 3), 255, np.uint8)
+    if n == 0 or K == 0:
+        return np.broadcast_to(white, (K, h, w, 3)).copy()
+    verts = verts_tran.float()
+    dev = verts.device
+    # the z of Rx(tilt) . Ry(azimuth) . centroid per view: (K,n), float64 (the bbox centre shifts every person alike)
+    cen = verts.double().mean(1)
+    ang = torch.from_numpy(np.radians(az)).to(dev)
+    ct, st = float(np.cos(np.radians(tilt))), float(np.sin(np.radians(tilt)))
+    z = cen[None, :, 1] * st + (cen[None, :, 2] * torch.cos(ang)[:, None] - cen[None, :, 0] * torch.sin(ang)[:, None]) * ct
+    order = torch.argsort(z, dim=1, stable=True)
+    views = turntable_views(verts, az, float(tilt), (h, w), expand_ratio=1.2, order=order)[0]
+    palette = np.asarray(mesh_colors).reshape(-1, 3)
+    return renderer.render_canvases(views.reshape(K * n, verts.shape[1], 3), triangles, white, np.arange(K + 1) * n,
+                                    mesh_colors=palette[np.arange(n) % len(palette)], vert_colors=vert_colors,
+                                    rows=order.reshape(-1))
+
+
+def render_mesh_frames(renderer, verts_camed_org, cam_trans, batch_ids, frames, triangles, mesh_color='identity', track_ids=None,
+                       part_labels=None):
+    """[romp_amd] The 'mesh' panel of `rendering_romp_bev_results` for the B same-sized frames of a batch in one render call
+    and one download: frames (B,h,w,3) uint8 (numpy or device), persons verts_camed_org (N,V,3) (device, already projected to
+    their frames) with cam_trans (N,3) and batch_ids (N,) ascending frame indices, as `forward_batch` returns them.  Per frame
+    the persons are painted far to near (cam_trans[:, 2] descending, z negated) and coloured as that function colours them in
+    an image of its own: `mesh_color` 'identity' is left to right WITHIN the frame.  -> (B,h,w,3) uint8 numpy; a frame without
+    persons comes back unchanged.  (cam_trans and batch_ids, a few floats per person, are read back to order the persons.)"""
+    B = len(frames)
+    ct = (cam_trans.detach() if torch.is_tensor(cam_trans) else torch.from_numpy(np.asarray(cam_trans))).cpu().float()
+    ids = (batch_ids.detach().cpu().numpy() if torch.is_tensor(batch_ids) else np.asarray(batch_ids)).reshape(-1).astype(np.int64)
+    tids = None if track_ids is None else (track_ids.cpu().numpy() if torch.is_tensor(track_ids) else np.asarray(track_ids)).reshape(-1)
+    perm, colors, offsets, part_colors = [], [], [0], None
+    for b in range(B):
+        idx = np.nonzero(ids == b)[0]
+        if len(idx):
+            mesh_colors, part_colors = _mesh_colors(mesh_color, ct[idx], None if tids is None else tids[idx], part_labels)
+            depth_order = torch.sort(ct[idx][:, 2], descending=True).indices.numpy()
+            perm.append(idx[depth_order])
+            colors.append(np.asarray(mesh_colors)[depth_order])
+        offsets.append(offsets[-1] + len(idx))
+    if not perm:
+        return renderer.render_canvases(verts_camed_org[:0], triangles, frames, offsets)
+    perm = torch.from_numpy(np.concatenate(perm))
+    vertices = verts_camed_org[perm.to(verts_camed_org.device)].clone()
+    vertices[:, :, 2] = vertices[:, :, 2] * -1
+    return renderer.render_canvases(vertices, triangles, frames, offsets, mesh_colors=np.concatenate(colors),
+                                    vert_colors=_per_person(part_colors, vertices))
 
 
 def _per_person(part_colors, verts):
