@@ -472,6 +472,7 @@ int launch_fusesum(const FuseTerm* terms, int n_terms, float* out, int B, int H,
     for (int k = 0; k < n_terms; ++k) {
         ROMP_REQUIRE((terms[k].cstride & 3) == 0, "fusesum: term stride must be float4 aligned");
         ROMP_REQUIRE((H >> terms[k].shift) << terms[k].shift == H, "fusesum: term %d shift %d does not divide H", k, terms[k].shift);
+        ROMP_REQUIRE((W >> terms[k].shift) << terms[k].shift == W, "fusesum: term %d shift %d does not divide W", k, terms[k].shift);
         ROMP_REQUIRE(terms[k].fmt != ROMP_FMT_H2 || (terms[k].cstride & 7) == 0, "fusesum: H2 term stride must be octet aligned");
         p.t[k] = terms[k].ptr; p.shift[k] = terms[k].shift; p.cs[k] = terms[k].cstride; p.h2[k] = terms[k].fmt == ROMP_FMT_H2;
     }

@@ -193,6 +193,45 @@ CONV_CASES = [
 CONV_PARAMS = [(c, f) for f in ('f32', 'h2') for c in CONV_CASES if not (f == 'h2' and c[0] % 16)]
 
 
+def _lower_conv_layer(dev, case, H, W, w, scale, shift, fmt):
+    """One fused conv+BN(+res)(+ReLU) layer of CONV_CASES' form on an H x W map, lowered with every weight pack (the bf16x3 and
+    f16x2 variants join a sweep over romp_conv_describe); fmt='h2': input / residual / output tensors in the pre-split H2 format.
+    -> (program, op, output is H2)."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, set_conv_math, ACT_SHIFT
+    cin, cout, k, s = case[:4]
+    relu, use_res = case[5:7]
+    relu_from = case[7] if len(case) > 7 else 0
+    Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
+    P = Program(dev)
+    set_conv_math(P, 'all')              # pack the split weights too: bf16x3 and f16x2 variants join the sweep below
+    xa = Act(0, cin, H, W, cin)
+    P.buf_floats.append(cin * H * W)
+    ra = None
+    if use_res:
+        P.buf_floats.append(cout * Ho * Wo)
+        ra = Act(1, cout, Ho, Wo, cout)
+    P.conv('t', xa, [w], [scale], [shift], k, s, relu, res=ra, relu_from=relu_from)
+    op = P.ops[0]
+    assert op.relu_from == relu_from
+    out_h2 = False
+    if fmt == 'h2':
+        assert cin % 8 == 0 and op.weight_h2, 'layer cannot read an H2 tensor (Cin %d)' % cin
+        out_h2 = op.Cout == op.cout_pad and cout % 8 == 0
+        op.act_shift = ACT_SHIFT
+        op.in_fmt = L.FMT_H2
+        op.out_fmt = L.FMT_H2 if out_h2 else L.FMT_F32
+        op.res_fmt = L.FMT_H2 if (out_h2 and use_res) else L.FMT_F32
+    return P, op, out_h2
+
+
+def _conv_variants(lib, op, B):
+    """The indices of the kernel variants romp_conv_describe accepts for the layer."""
+    import ctypes as C
+    buf = C.create_string_buffer(128)
+    return [v for v in range(lib.romp_conv_num_variants()) if lib.romp_conv_describe(C.byref(op), B, v, buf, 128) == 0]
+
+
 @pytest.mark.parametrize('case,fmt', CONV_PARAMS, ids=lambda v: v if isinstance(v, str) else 'c%d_%d_k%d_s%d_h%d' % v[:5])
 @pytest.mark.parametrize('B', [1, 3])
 def test_conv_layer(dev, case, B, fmt):
@@ -201,7 +240,7 @@ def test_conv_layer(dev, case, B, fmt):
     pre-split H2 format (only the f16x2 kernels read it; every kernel family's epilogue can write it)."""
     import ctypes as C
     from romp_amd import lib as L
-    from romp_amd.plan import Program, Act, set_conv_math, encode_h2, decode_h2, ACT_SHIFT
+    from romp_amd.plan import encode_h2, decode_h2
     cin, cout, k, s, H, relu, use_res = case[:7]
     relu_from = case[7] if len(case) > 7 else 0
     g = torch.Generator().manual_seed(cin * 1000 + cout + k + s + H)
@@ -218,25 +257,8 @@ def test_conv_layer(dev, case, B, fmt):
     if relu:
         ref = torch.cat([ref[:, :relu_from], torch.relu(ref[:, relu_from:])], 1)
     ref = ref.permute(0, 2, 3, 1)
-    P = Program(dev)
-    set_conv_math(P, 'all')              # pack the split weights too: bf16x3 and f16x2 variants join the sweep below
-    xa = Act(0, cin, H, H, cin)
-    P.buf_floats.append(cin * H * H)
-    ra = None
-    if res is not None:
-        P.buf_floats.append(cout * Ho * Ho)
-        ra = Act(1, cout, Ho, Ho, cout)
-    P.conv('t', xa, [w], [scale], [shift], k, s, relu, res=ra, relu_from=relu_from)
-    op = P.ops[0]
-    assert op.relu_from == relu_from
-    out_h2 = False
+    P, op, out_h2 = _lower_conv_layer(dev, case, H, H, w, scale, shift, fmt)
     if fmt == 'h2':
-        assert cin % 8 == 0 and op.weight_h2, 'layer cannot read an H2 tensor (Cin %d)' % cin
-        out_h2 = op.Cout == op.cout_pad and cout % 8 == 0
-        op.act_shift = ACT_SHIFT
-        op.in_fmt = L.FMT_H2
-        op.out_fmt = L.FMT_H2 if out_h2 else L.FMT_F32
-        op.res_fmt = L.FMT_H2 if (out_h2 and res is not None) else L.FMT_F32
         x_in = encode_h2(x)
         res_in = encode_h2(res) if (res is not None and op.res_fmt == L.FMT_H2) else res
     else:
@@ -244,8 +266,7 @@ def test_conv_layer(dev, case, B, fmt):
     xd, rd = x_in.to(dev), (res_in.to(dev) if res_in is not None else None)
     lib = L.load()
     buf = C.create_string_buffer(128)
-    runs = ([(1, -1)] if fmt == 'f32' else []) + [(0, -1)] + [(0, v) for v in range(lib.romp_conv_num_variants())
-                                                                if lib.romp_conv_describe(C.byref(op), B, v, buf, 128) == 0]
+    runs = ([(1, -1)] if fmt == 'f32' else []) + [(0, -1)] + [(0, v) for v in _conv_variants(lib, op, B)]
     assert len(runs) >= 2
     for mode, variant in runs:
         out = torch.full((B, Ho, Ho, cout), float('nan'), device=dev)
@@ -390,29 +411,31 @@ def test_fused_basic_block_strip(dev, B, H, Cc, run, monkeypatch):
     _fused_basic_block(dev, B, H, Cc, 'r', monkeypatch)
 
 
-def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch):
+def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch, W=None, run=True, ref_dtype=torch.float32):
     """csrc/conv_h2b.hip ('v1', 32 channels) / conv_h2c.h ('r', 32 and 64 channels): a BasicBlock as ONE launch (intermediate tile in LDS).  A three-conv program -- an
     ordinary conv producing the H2 block input, then the block -- lowered by plan.py (which must fuse the pair), run through
     romp_net_create / romp_net_forward, against torch on the CPU: image borders (the intermediate's zero padding), interior
-    tiles, odd tile counts, batch > 1.  Same bound as the single layers, two layers deeper: 5e-5 of the output's magnitude."""
+    tiles, odd tile counts, batch > 1.  Same bound as the single layers, two layers deeper: 5e-5 of the output's magnitude.
+    W: the map's width (default: square); run=False: lower and check the fusion only (no device; -> the program); ref_dtype: the reference's arithmetic."""
     import ctypes as C
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act, set_conv_math, decode_h2
     monkeypatch.setenv('ROMP_FUSE_BLOCKS', 'all')
+    W = H if W is None else W
     g = torch.Generator().manual_seed(100 * B + H + Cc)
-    x = torch.randn(B, H, H, Cc, generator=g)
+    x = torch.randn(B, H, W, Cc, generator=g)
     ws = [torch.randn(Cc, Cc, 3, 3, generator=g) / (Cc * 9) ** 0.5 for _ in range(3)]
     sc = [torch.rand(Cc, generator=g) + 0.5 for _ in range(3)]
     sh = [torch.randn(Cc, generator=g) * 0.2 for _ in range(3)]
 
     def cbr(t, i, res=None):
-        y = F.conv2d(t, ws[i], None, padding=1) * sc[i].view(1, -1, 1, 1) + sh[i].view(1, -1, 1, 1)
+        y = F.conv2d(t, ws[i].to(ref_dtype), None, padding=1) * sc[i].to(ref_dtype).view(1, -1, 1, 1) + sh[i].to(ref_dtype).view(1, -1, 1, 1)
         return torch.relu(y if res is None else y + res)
-    t0 = cbr(x.permute(0, 3, 1, 2), 0)
-    ref = cbr(cbr(t0, 1), 2, res=t0).permute(0, 2, 3, 1)
+    t0 = cbr(x.permute(0, 3, 1, 2).to(ref_dtype), 0)
+    ref = cbr(cbr(t0, 1), 2, res=t0).permute(0, 2, 3, 1).float()
     P = Program(dev)
     set_conv_math(P, 'f16x2')
-    a0 = P.conv('c0', Act(L.BUF_IMAGE, Cc, H, H, Cc), [ws[0]], [sc[0]], [sh[0]], 3, 1, True)
+    a0 = P.conv('c0', Act(L.BUF_IMAGE, Cc, H, W, Cc), [ws[0]], [sc[0]], [sh[0]], 3, 1, True)
     a1 = P.conv('c1', a0, [ws[1]], [sc[1]], [sh[1]], 3, 1, True)
     a2 = P.conv('c2', a1, [ws[2]], [sc[2]], [sh[2]], 3, 1, True, res=a0)
     ops = P.op_array()
@@ -424,6 +447,8 @@ def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch):
         ops[2].flags &= ~L.OPF_WAVE16
     else:                                                    # conv_h2c.h's row-pipelined kernels
         assert ops[1].weight_aux and ops[2].weight_aux and (ops[1].flags & ops[2].flags & L.OPF_WAVE16)
+    if not run:
+        return P
     lib = L.load()
     h = C.c_void_p()
     sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
@@ -437,9 +462,9 @@ def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch):
             L.check(lib.romp_net_forward(h, L.ptr(xd), B, L.ptr(dummy), L.ptr(dummy), L.stream_ptr(dev)))
             L.check(lib.romp_net_read_buffer(h, a2.buf, B, L.ptr(out), n, L.stream_ptr(dev)))
             torch.cuda.synchronize()
-            y = decode_h2(out.cpu().reshape(B, H, H, Cc))
+            y = decode_h2(out.cpu().reshape(B, H, W, Cc))
             err = (y - ref).abs().max().item() / ref.abs().max().item()
-            print(f'fused BasicBlock B={B} {H}x{H}x{Cc} run {rep}: relative err {err:.3e}')
+            print(f'fused BasicBlock B={B} {H}x{W}x{Cc} run {rep}: relative err {err:.3e}')
             assert err < 5e-5, err
     finally:
         lib.romp_net_destroy(h)
@@ -447,29 +472,35 @@ def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch):
 
 @pytest.mark.parametrize('CO,NUP,ND,H,B', [(32, 1, 1, 64, 1), (32, 2, 1, 64, 3), (32, 3, 1, 128, 2), (64, 1, 2, 32, 3), (64, 2, 2, 64, 2), (128, 1, 3, 32, 3)])
 def test_fuseup(dev, CO, NUP, ND, H, B):
+    _fuseup(dev, CO, NUP, ND, H, B)
+
+
+def _fuseup(dev, CO, NUP, ND, H, B, W=None, run=True, ref_dtype=torch.float32):
     """csrc/conv_fup.hip (ROMP_OP_FUSEUP): a fuse-layer output with its 1x1 up-convs inside, lowered by plan.fuse_up_sums from the
     ordinary [1x1 convs ..., fusesum] form -- here with the up-convs MERGED over two outputs like plan.hr_module emits them (the
     output under test takes channel slice [16 : 16 + CO) of each) -- against torch: y = relu(sum of ND direct tensors +
     sum_k up_{2^k}(bn_k(W_k x_k))), x_k with CO << k channels at 1 / 2^k of the resolution.  HRNet's production shapes and small ones,
-    B > 1, every instantiation of the kernel."""
+    B > 1, every instantiation of the kernel.  W: the map's width (default: square); run=False: lower and check the fusion only (no device; -> the program);
+    ref_dtype: the reference's arithmetic."""
     import ctypes as C
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act, set_conv_math, decode_h2
     g = torch.Generator().manual_seed(CO + 10 * NUP + H)
+    W = H if W is None else W
     cin0 = 32
-    img = torch.randn(B, H, H, cin0, generator=g)
+    img = torch.randn(B, H, W, cin0, generator=g)
 
     def mk(co, ci, k):
         return (torch.randn(co, ci, k, k, generator=g) / (ci * k * k) ** 0.5, torch.rand(co, generator=g) + 0.5, torch.randn(co, generator=g) * 0.2)
 
     def tconv(t, wsb, stride, relu):
         w, sc, sh = wsb
-        y = F.conv2d(t, w, None, stride=stride, padding=w.shape[-1] // 2) * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)
+        y = F.conv2d(t, w.to(ref_dtype), None, stride=stride, padding=w.shape[-1] // 2) * sc.to(ref_dtype).view(1, -1, 1, 1) + sh.to(ref_dtype).view(1, -1, 1, 1)
         return torch.relu(y) if relu else y
     P = Program(dev)
     set_conv_math(P, 'f16x2')
-    x_img = Act(L.BUF_IMAGE, cin0, H, H, cin0)
-    xin = img.permute(0, 3, 1, 2)
+    x_img = Act(L.BUF_IMAGE, cin0, H, W, cin0)
+    xin = img.permute(0, 3, 1, 2).to(ref_dtype)
     # sources: x_0 (CO @ H, a direct term), x_k (CO << k @ H >> k): a chain of stride-2 convs; extra direct terms from x_0
     srcs_w = [mk(CO, cin0, 3)] + [mk(CO << k, CO << (k - 1), 3) for k in range(1, NUP + 1)]
     acts, refs = [], []
@@ -496,12 +527,14 @@ def test_fuseup(dev, CO, NUP, ND, H, B):
     ref = dref[0]
     for t in dref[1:] + uref:
         ref = ref + t
-    ref = torch.relu(ref).permute(0, 2, 3, 1)
+    ref = torch.relu(ref).permute(0, 2, 3, 1).float()
     ops = P.op_array()
     assert P.fused_ups == 1, 'plan.fuse_up_sums must fuse the output (kinds %s)' % [o.kind for o in P.ops]
     fup = [o for o in P.ops if o.kind == L.OP_FUSEUP][0]
     assert [o.kind for o in P.ops if o.kind == L.OP_FUSESUM] == [] and sum(o.kind == L.OP_NOP for o in P.ops) == NUP
     assert fup.out_fmt == L.FMT_H2 and fup.n_terms == ND + NUP
+    if not run:
+        return P
     lib = L.load()
     h = C.c_void_p()
     sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
@@ -515,9 +548,9 @@ def test_fuseup(dev, CO, NUP, ND, H, B):
             L.check(lib.romp_net_forward(h, L.ptr(xd), B, L.ptr(dummy), L.ptr(dummy), L.stream_ptr(dev)))
             L.check(lib.romp_net_read_buffer(h, out.buf, B, L.ptr(got), n, L.stream_ptr(dev)))
             torch.cuda.synchronize()
-            y = decode_h2(got.cpu().reshape(B, H, H, CO))
+            y = decode_h2(got.cpu().reshape(B, H, W, CO))
             err = (y - ref).abs().max().item() / ref.abs().max().item()
-            print(f'fuseup CO={CO} NUP={NUP} ND={ND} B={B} {H}x{H} run {rep}: relative err {err:.3e}')
+            print(f'fuseup CO={CO} NUP={NUP} ND={ND} B={B} {H}x{W} run {rep}: relative err {err:.3e}')
             assert err < 5e-5, err
     finally:
         lib.romp_net_destroy(h)
@@ -1303,17 +1336,33 @@ def test_graph_cache_is_bounded(dev):
     assert all(torch.equal(c, c0) and torch.equal(p, p0) for c, p in keep)
 
 
+def _seam_views(H, W):
+    """The ordinary 1x1 convs around a seam need a map of whole 16-column tiles, the seam kernel only a pixel count: on a narrower /
+    odd-width map they see the same (contiguous NHWC, pointwise) pixels as an (H * W / 16) x 16 map.  -> (that shape, as_map(act, shape):
+    the same tensor declared with another shape)."""
+    import dataclasses
+    view = (H, W) if W % 16 == 0 else (H * W // 16, 16)
+    assert view[0] * view[1] == H * W
+    return view, lambda act, hw: dataclasses.replace(act, H=hw[0], W=hw[1])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('B,H', [(1, 16), (3, 32), (2, 128)])            # (2, 128): layer1's production shape
 def test_seam1x1(dev, B, H, monkeypatch):
+    _seam1x1(dev, B, H, monkeypatch)
+
+
+def _seam1x1(dev, B, H, monkeypatch, W=None, run=True):
     """csrc/conv_h2x.hip: the 1x1 64 -> 256 (+ residual + ReLU) / 1x1 256 -> 64 (+ ReLU) pair across
-    a Bottleneck seam as one launch: both output tensors against torch on the CPU."""
+    a Bottleneck seam as one launch: both output tensors against torch on the CPU.  W: the map's width (default: square);
+    run=False: lower and check the fusion only (no device; -> the program)."""
     import ctypes as C
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act, set_conv_math, decode_h2
     monkeypatch.setenv('ROMP_FUSE_SEAMS', '1')
+    W = H if W is None else W
     g = torch.Generator().manual_seed(7 * B + H)
-    x0 = torch.randn(B, H, H, 64, generator=g)
+    x0 = torch.randn(B, H, W, 64, generator=g)
     dims = [(64, 256), (256, 64), (64, 256), (256, 64), (64, 64)]
     ws = [torch.randn(co, ci, 1, 1, generator=g) / ci ** 0.5 for ci, co in dims]
     sc = [torch.rand(co, generator=g) + 0.5 for _, co in dims]
@@ -1328,13 +1377,17 @@ def test_seam1x1(dev, B, H, monkeypatch):
     ru = cbr(rt, 3)
     P = Program(dev)
     set_conv_math(P, 'f16x2')
-    ax = P.conv('x', Act(L.BUF_IMAGE, 64, H, H, 64), [ws[0]], [sc[0]], [sh[0]], 1, 1, True)
+    view, as_map = _seam_views(H, W)                        # (H, W) itself on maps of whole 16-column tiles
+    ax = P.conv('x', Act(L.BUF_IMAGE, 64, view[0], view[1], 64), [ws[0]], [sc[0]], [sh[0]], 1, 1, True)
     am = P.conv('m', ax, [ws[1]], [sc[1]], [sh[1]], 1, 1, True)
-    at = P.conv('t', am, [ws[2]], [sc[2]], [sh[2]], 1, 1, True, res=ax)
+    at = P.conv('t', as_map(am, (H, W)), [ws[2]], [sc[2]], [sh[2]], 1, 1, True, res=as_map(ax, (H, W)))
     au = P.conv('u', at, [ws[3]], [sc[3]], [sh[3]], 1, 1, True)
-    av = P.conv('v', au, [ws[4]], [sc[4]], [sh[4]], 1, 1, True)
+    av = P.conv('v', as_map(au, view), [ws[4]], [sc[4]], [sh[4]], 1, 1, True)
     ops = P.op_array()
     assert P.fused_seams == 1 and [o.kind for o in P.ops] == [L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_SEAM1X1, L.OP_CONV], [o.kind for o in P.ops]
+    assert (P.ops[3].H, P.ops[3].W) == (H, W)
+    if not run:
+        return P
     lib = L.load()
     h = C.c_void_p()
     sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
@@ -1348,10 +1401,10 @@ def test_seam1x1(dev, B, H, monkeypatch):
             out = torch.empty(n, device=dev)
             L.check(lib.romp_net_read_buffer(h, act.buf, B, L.ptr(out), n, L.stream_ptr(dev)))
             torch.cuda.synchronize()
-            y = decode_h2(out.cpu().reshape(B, H, H, act.C))
+            y = decode_h2(out.cpu().reshape(B, H, W, act.C))
             r = ref.permute(0, 2, 3, 1)
             err = (y - r).abs().max().item() / r.abs().max().item()
-            print(f'seam1x1 B={B} {H}x{H} {name}: relative err {err:.3e}')
+            print(f'seam1x1 B={B} {H}x{W} {name}: relative err {err:.3e}')
             assert err < 5e-5, (name, err)
     finally:
         lib.romp_net_destroy(h)
@@ -1360,16 +1413,22 @@ def test_seam1x1(dev, B, H, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize('B,H', [(1, 16), (3, 32), (2, 128)])
 def test_seam1x1_downsample(dev, B, H, monkeypatch):
+    _seam1x1_downsample(dev, B, H, monkeypatch)
+
+
+def _seam1x1_downsample(dev, B, H, monkeypatch, W=None, run=True):
     """csrc/conv_h2x.hip, DS = 1 (round 5, OPF_SEAM_DS): the seam behind Bottleneck 0 -- t = relu(bn3(conv1x1(m)) + bn_d(conv1x1(x0))),
     the residual being the block's own `downsample` conv of the block input (model.py:289-301) -- as one launch that never
     materialises the downsample output; both outputs against torch on the CPU, and against the ROMP_SEAM_DS=0 lowering of the
-    same program (the downsample as a launch of its own)."""
+    same program (the downsample as a launch of its own).  W: the map's width (default: square); run=False: lower and check the
+    fusion only (no device; -> the two programs)."""
     import ctypes as C
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act, set_conv_math, decode_h2
     monkeypatch.setenv('ROMP_FUSE_SEAMS', '1')
+    W = H if W is None else W
     g = torch.Generator().manual_seed(11 * B + H)
-    img = torch.randn(B, H, H, 64, generator=g)
+    img = torch.randn(B, H, W, 64, generator=g)
     dims = [(64, 64), (64, 64), (64, 256), (64, 256), (256, 64), (64, 64)]      # x0, m, downsample, conv3, next conv1, a reader of u
     ws = [torch.randn(co, ci, 1, 1, generator=g) / ci ** 0.5 for ci, co in dims]
     sc = [torch.rand(co, generator=g) + 0.5 for _, co in dims]
@@ -1389,19 +1448,25 @@ def test_seam1x1_downsample(dev, B, H, monkeypatch):
         monkeypatch.setenv('ROMP_SEAM_DS', ds)
         P = Program(dev)
         set_conv_math(P, 'f16x2')
-        a0 = P.conv('x0', Act(L.BUF_IMAGE, 64, H, H, 64), [ws[0]], [sc[0]], [sh[0]], 1, 1, True)
+        view, as_map = _seam_views(H, W)                    # (H, W) itself on maps of whole 16-column tiles
+        dmap = (H, W) if ds == '1' else view                # the downsample conv: folded into the seam / a launch of its own
+        a0 = P.conv('x0', Act(L.BUF_IMAGE, 64, view[0], view[1], 64), [ws[0]], [sc[0]], [sh[0]], 1, 1, True)
         am = P.conv('m', a0, [ws[1]], [sc[1]], [sh[1]], 1, 1, True)
-        ad = P.conv('d', a0, [ws[2]], [sc[2]], [sh[2]], 1, 1, False)
-        at = P.conv('t', am, [ws[3]], [sc[3]], [sh[3]], 1, 1, True, res=ad)
+        ad = P.conv('d', as_map(a0, dmap), [ws[2]], [sc[2]], [sh[2]], 1, 1, False)
+        at = P.conv('t', as_map(am, (H, W)), [ws[3]], [sc[3]], [sh[3]], 1, 1, True, res=as_map(ad, (H, W)))
         au = P.conv('u', at, [ws[4]], [sc[4]], [sh[4]], 1, 1, True)
-        av = P.conv('v', au, [ws[5]], [sc[5]], [sh[5]], 1, 1, True)
+        av = P.conv('v', as_map(au, view), [ws[5]], [sc[5]], [sh[5]], 1, 1, True)
         ops = P.op_array()
         kinds = [o.kind for o in P.ops]
+        assert (P.ops[4].H, P.ops[4].W) == (H, W)
         if ds == '1':
             assert P.fused_seams == 1 and P.folded_downsamples == 1 and kinds == [L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_NOP, L.OP_SEAM1X1, L.OP_CONV], kinds
             assert P.ops[4].flags & L.OPF_SEAM_DS
         else:
             assert P.fused_seams == 1 and kinds == [L.OP_CONV, L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_SEAM1X1, L.OP_CONV], kinds
+        if not run:
+            outs[ds] = P
+            continue
         lib = L.load()
         h = C.c_void_p()
         sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
@@ -1415,14 +1480,16 @@ def test_seam1x1_downsample(dev, B, H, monkeypatch):
                 out = torch.empty(n, device=dev)
                 L.check(lib.romp_net_read_buffer(h, act.buf, B, L.ptr(out), n, L.stream_ptr(dev)))
                 torch.cuda.synchronize()
-                y = decode_h2(out.cpu().reshape(B, H, H, act.C))
+                y = decode_h2(out.cpu().reshape(B, H, W, act.C))
                 r = ref.permute(0, 2, 3, 1)
                 err = (y - r).abs().max().item() / r.abs().max().item()
-                print(f'seam1x1 ds={ds} B={B} {H}x{H} {name}: relative err {err:.3e}')
+                print(f'seam1x1 ds={ds} B={B} {H}x{W} {name}: relative err {err:.3e}')
                 assert err < 5e-5, (ds, name, err)
                 outs[(ds, name)] = y
         finally:
             lib.romp_net_destroy(h)
+    if not run:
+        return [outs['1'], outs['0']]
     for name in ('t', 'u'):                                      # the two lowerings agree to float32 rounding (the fold adds in float32 what
         d = (outs[('1', name)] - outs[('0', name)]).abs().max().item()      # the separate launch rounds to two fp16 pieces first)
         assert d < 2e-5 * max(1.0, outs[('0', name)].abs().max().item()), (name, d)

@@ -95,12 +95,18 @@ def test_stem7p_falls_back_to_the_float32_pair(dev, monkeypatch):
 
 @pytest.mark.parametrize('cin,cout,H', [(2048, 256, 16), (256, 128, 32), (128, 64, 64)])
 def test_transposed_conv_as_parity_convs(dev, cin, cout, H):
-    """ConvTranspose2d(k4, s2, p1) + BN + ReLU (resnet_50.py:93-120) == four 2x2 convs writing interleaved."""
+    _parity_convs(dev, cin, cout, H)
+
+
+def _parity_convs(dev, cin, cout, H, W=None):
+    """ConvTranspose2d(k4, s2, p1) + BN + ReLU (resnet_50.py:93-120) == four 2x2 convs writing interleaved.  W: the input map's
+    width (default: square)."""
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act
     B = 2
+    W = H if W is None else W
     g = torch.Generator().manual_seed(cin)
-    x = torch.randn(B, cin, H, H, generator=g)
+    x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cin, cout, 4, 4, generator=g) / (cin * 4) ** 0.5
     scale, shift = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
     ref = torch.relu(F.conv_transpose2d(x, w, None, stride=2, padding=1) * scale[None, :, None, None] + shift[None, :, None, None])
@@ -108,39 +114,44 @@ def test_transposed_conv_as_parity_convs(dev, cin, cout, H):
     lib = L.load()
     KY = ((3, 1), (2, 0))
     xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
-    H2 = 2 * H
+    H2, W2 = 2 * H, 2 * W
     worst = {}
     for bx3 in ((False, True) if L.has_bf16x3() else (False,)):      # (the bf16x3 family is optional since round 6)
         P = Program(dev)
         P.bf16x3 = bx3
-        P.buf_floats += [cin * H * H, cout * H2 * H2]
+        P.buf_floats += [cin * H * W, cout * H2 * W2]
         for a in range(2):
             for b in range(2):
                 w2 = torch.stack([torch.stack([w[:, :, KY[a][dy], KY[b][dx]] for dx in range(2)], -1) for dy in range(2)], -2).permute(1, 0, 2, 3).contiguous()
-                P.conv(f'p{a}{b}', Act(0, cin, H, H, cin), [w2], [scale], [shift], 2, 1, True, out_buf_special=1, out_cstride=2 * cout,
-                       out_coff=a * H2 * cout + b * cout, pad=(1 - a, 1 - b), out_rstride=2 * H2 * cout, out_bstride=H2 * H2 * cout)
+                P.conv(f'p{a}{b}', Act(0, cin, H, W, cin), [w2], [scale], [shift], 2, 1, True, out_buf_special=1, out_cstride=2 * cout,
+                       out_coff=a * W2 * cout + b * cout, pad=(1 - a, 1 - b), out_rstride=2 * W2 * cout, out_bstride=H2 * W2 * cout)
         runs = [(1, -1), (0, -1)] + _variants(lib, P.ops[0], B)
         for mode, variant in runs:
-            out = torch.full((B, H2, H2, cout), float('nan'), device=dev)
+            out = torch.full((B, H2, W2, cout), float('nan'), device=dev)
             for op in P.ops:
                 L.check(lib.romp_conv_forward(C.byref(op), L.ptr(xd), None, L.ptr(out), B, mode, variant, L.stream_ptr(dev)))
             torch.cuda.synchronize()
             err = (out.cpu() - ref).abs().max().item()
             worst[(bx3, mode, variant)] = err
             assert err < 5e-5, (bx3, mode, variant, err)
-    print('deconv %d->%d @%d: %d kernel variants, worst max-abs %.2e' % (cin, cout, H, len(worst), max(worst.values())))
+    print('deconv %d->%d @%dx%d: %d kernel variants, worst max-abs %.2e' % (cin, cout, H, W, len(worst), max(worst.values())))
 
 
 @pytest.mark.parametrize('cin,cout,H', [(2048, 256, 16), (256, 128, 32), (128, 64, 64)])
 def test_transposed_conv_as_parity_convs_h2(dev, cin, cout, H):
+    _parity_convs_h2(dev, cin, cout, H)
+
+
+def _parity_convs_h2(dev, cin, cout, H, W=None):
     """The same four parity convs on pre-split H2 tensors (what the f16x2 program runs): every kernel variant that can take the layer
     -- the generic f16x2 kernels and csrc/conv_h2g.hip's K = 4 taps x Cin form -- writes its parity of the interleaved H2 output
-    through the sparse output strides; the decoded tensor against torch's ConvTranspose2d."""
+    through the sparse output strides; the decoded tensor against torch's ConvTranspose2d.  W: the input map's width (default: square)."""
     from romp_amd import lib as L
     from romp_amd.plan import Program, Act, set_conv_math, encode_h2, decode_h2, ACT_SHIFT
     B = 2
+    W = H if W is None else W
     g = torch.Generator().manual_seed(cin + 1)
-    x = torch.randn(B, cin, H, H, generator=g)
+    x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cin, cout, 4, 4, generator=g) / (cin * 4) ** 0.5
     scale, shift = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
     ref = torch.relu(F.conv_transpose2d(x, w, None, stride=2, padding=1) * scale[None, :, None, None] + shift[None, :, None, None])
@@ -148,22 +159,22 @@ def test_transposed_conv_as_parity_convs_h2(dev, cin, cout, H):
     lib = L.load()
     KY = ((3, 1), (2, 0))
     xd = encode_h2(x.permute(0, 2, 3, 1).contiguous()).to(dev)
-    H2 = 2 * H
+    H2, W2 = 2 * H, 2 * W
     P = Program(dev)
     set_conv_math(P, 'f16x2')
-    P.buf_floats += [cin * H * H, cout * H2 * H2]
+    P.buf_floats += [cin * H * W, cout * H2 * W2]
     for a in range(2):
         for b in range(2):
             w2 = torch.stack([torch.stack([w[:, :, KY[a][dy], KY[b][dx]] for dx in range(2)], -1) for dy in range(2)], -2).permute(1, 0, 2, 3).contiguous()
-            P.conv(f'p{a}{b}', Act(0, cin, H, H, cin), [w2], [scale], [shift], 2, 1, True, out_buf_special=1, out_cstride=2 * cout,
-                   out_coff=a * H2 * cout + b * cout, pad=(1 - a, 1 - b), out_rstride=2 * H2 * cout, out_bstride=H2 * H2 * cout)
+            P.conv(f'p{a}{b}', Act(0, cin, H, W, cin), [w2], [scale], [shift], 2, 1, True, out_buf_special=1, out_cstride=2 * cout,
+                   out_coff=a * W2 * cout + b * cout, pad=(1 - a, 1 - b), out_rstride=2 * W2 * cout, out_bstride=H2 * W2 * cout)
     for op in P.ops:
         assert op.weight_h2
         op.act_shift, op.in_fmt, op.out_fmt = ACT_SHIFT, L.FMT_H2, L.FMT_H2
     buf = C.create_string_buffer(128)
     names = {}
     for mode, variant in [(0, -1)] + _variants(lib, P.ops[0], B):
-        out = torch.full((B, H2, H2, cout), float('nan'), device=dev)
+        out = torch.full((B, H2, W2, cout), float('nan'), device=dev)
         for op in P.ops:
             L.check(lib.romp_conv_forward(C.byref(op), L.ptr(xd), None, L.ptr(out), B, mode, variant, L.stream_ptr(dev)))
         torch.cuda.synchronize()
@@ -172,7 +183,7 @@ def test_transposed_conv_as_parity_convs_h2(dev, cin, cout, H):
         names[buf.value.decode()] = err
         assert err < 5e-5, (buf.value, variant, err)
     assert any(n.startswith('conv_h2g_k2s1') for n in names), names
-    print('deconv (H2) %d->%d @%d: %s' % (cin, cout, H, ', '.join('%s %.1e' % kv for kv in sorted(names.items()))))
+    print('deconv (H2) %d->%d @%dx%d: %s' % (cin, cout, H, W, ', '.join('%s %.1e' % kv for kv in sorted(names.items()))))
 
 
 @pytest.mark.parametrize('cin,cout,H', [(256, 512, 128), (1024, 2048, 32)])
