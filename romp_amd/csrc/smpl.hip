@@ -18,22 +18,12 @@
 //   kernel C (one workgroup per person)  sums the 108 per-tile partials in a fixed order, picks 21 vertices,
 //            optional root alignment of the joints.
 // All float32; bound = HBM (constants 20 MB once + 82.7 KB written per person).
-#include "common.h"
+// The sizes, the pose kernel (kernel A), the posedirs chunk helpers of kernel B and smpl_ctx live in smpl_shared.h, which
+// the backward (smpl_grad.hip) includes too.
+#include "smpl_shared.h"
 #include <vector>
 
 namespace romp {
-
-constexpr int NV = 6890, NJ = 24, NPF = 207, NJOUT = 71, NREG = 26, NPICK = 21;
-constexpr int PB = 16;                                 // persons per workgroup in the skinning kernel
-constexpr int NT = (NV + 63) / 64;                    // 108 vertex tiles
-constexpr int MAXLV = NJ;
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }   // v_pk_fma_f32
-
-struct Parents { int p[NJ]; };
-// joints ordered by depth in the kinematic tree: level l = order[start[l] .. start[l + 1])
-struct Levels { int n; int start[MAXLV + 1]; int order[NJ]; };
 
 // J_template[j][k] = sum_v Jreg[j][v] v_template[v][k];  J_shapedirs[j][k][l] = sum_v Jreg[j][v] S[v][k][l]
 __global__ __launch_bounds__(256) void smpl_prep_kernel(const float* __restrict__ Jreg, const float* __restrict__ vt,
@@ -60,133 +50,12 @@ __global__ __launch_bounds__(256) void smpl_prep_kernel(const float* __restrict_
     }
 }
 
-// ---- kernel A: per-person pose prologue ---------------------------------------------------------
-// pose_feat is written in the layout the skinning kernel stages: [person group][207][PB]
-template <int NB>
-__global__ __launch_bounds__(64) void smpl_pose_kernel(const float* __restrict__ betas,
-                                                        const float* __restrict__ thetas,
-                                                        const float* __restrict__ Jt, const float* __restrict__ Js,
-                                                        const int* __restrict__ sched, float* __restrict__ pose_feat,
-                                                        float* __restrict__ Amat, float* __restrict__ joints) {
-    __shared__ float sR[NJ][9], sJ[NJ][3], sG[NJ][12];
-    const int n = blockIdx.x, lane = threadIdx.x;
-    if (lane < NJ) {
-        const float* r = thetas + (size_t)n * 72 + lane * 3;
-        const float rx0 = r[0], ry0 = r[1], rz0 = r[2];
-        float jt[3], js[3][NB], bt[NB];                      // every load of the prologue in flight before the first use
-#pragma unroll
-        for (int l = 0; l < NB; ++l) bt[l] = betas[(size_t)n * NB + l];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            jt[k] = Jt[lane * 3 + k];
-#pragma unroll
-            for (int l = 0; l < NB; ++l) js[k][l] = Js[(lane * 3 + k) * NB + l];
-        }
-        const float ex = rx0 + 1e-8f, ey = ry0 + 1e-8f, ez = rz0 + 1e-8f;     // smpl.py:206
-        const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-        const float rx = rx0 / angle, ry = ry0 / angle, rz = rz0 / angle;
-        float sn, cs;
-        sincosf(angle, &sn, &cs);
-        const float oc = 1.f - cs;
-        // K = [[0,-rz,ry],[rz,0,-rx],[-ry,rx,0]];  R = I + sin K + (1-cos) K K   (smpl.py:217-221)
-        const float kk00 = -(rz * rz) - ry * ry, kk11 = -(rz * rz) - rx * rx, kk22 = -(ry * ry) - rx * rx;
-        const float kk01 = ry * rx, kk02 = rz * rx, kk12 = rz * ry;
-        float R[9];
-        R[0] = 1.f + oc * kk00;      R[1] = sn * -rz + oc * kk01; R[2] = sn * ry + oc * kk02;
-        R[3] = sn * rz + oc * kk01;  R[4] = 1.f + oc * kk11;      R[5] = sn * -rx + oc * kk12;
-        R[6] = sn * -ry + oc * kk02; R[7] = sn * rx + oc * kk12;  R[8] = 1.f + oc * kk22;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) sR[lane][e] = R[e];
-        if (lane >= 1) {
-            float* pf = pose_feat + (size_t)(n / PB) * NPF * PB + (n % PB);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) pf[((lane - 1) * 9 + e) * PB] = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float a = jt[k];
-#pragma unroll
-            for (int l = 0; l < NB; ++l) a = fmaf(bt[l], js[k][l], a);
-            sJ[lane][k] = a;
-        }
-    }
-    __syncthreads();
-    // kinematic chain (smpl.py:269-275): G[i] = G[parent] * [R_i | J_i - J_parent], one tree level per step; five groups of
-    // 12 lanes each own one joint of the level (one element of its 3x4 transform per lane)
-    const int grp = lane / 12, el = lane % 12, rr = el / 4, cc = el % 4;
-    if (lane < 12) sG[0][lane] = (cc < 3) ? sR[0][rr * 3 + cc] : sJ[0][rr];
-    __syncthreads();
-    const int n_lv = sched[0];
-    for (int lv = 1; lv < n_lv; ++lv) {
-        const int q1 = sched[1 + lv + 1];
-        for (int q = sched[1 + lv] + grp; q < q1 && grp < 5; q += 5) {
-            const int i = sched[1 + (MAXLV + 1) + q], p = sched[1 + (MAXLV + 1) + NJ + i];
-            float v;
-            if (cc < 3) {
-                v = sG[p][rr * 4 + 0] * sR[i][0 * 3 + cc];
-                v = fmaf(sG[p][rr * 4 + 1], sR[i][1 * 3 + cc], v);
-                v = fmaf(sG[p][rr * 4 + 2], sR[i][2 * 3 + cc], v);
-            } else {
-                v = sG[p][rr * 4 + 0] * (sJ[i][0] - sJ[p][0]);
-                v = fmaf(sG[p][rr * 4 + 1], sJ[i][1] - sJ[p][1], v);
-                v = fmaf(sG[p][rr * 4 + 2], sJ[i][2] - sJ[p][2], v);
-                v += sG[p][rr * 4 + 3];
-            }
-            sG[i][el] = v;
-        }
-        __syncthreads();
-    }
-    // posed joints + relative transforms A = G - pad(G [J;0])   (smpl.py:280-288)
-    for (int idx = lane; idx < NJ * 12; idx += 64) {
-        const int j = idx / 12, e = idx % 12, r = e / 4, c = e % 4;
-        float v = sG[j][e];
-        if (c == 3) {
-            joints[((size_t)n * NJOUT + j) * 3 + r] = v;
-            const float t = sG[j][r * 4 + 0] * sJ[j][0] + sG[j][r * 4 + 1] * sJ[j][1] + sG[j][r * 4 + 2] * sJ[j][2];
-            v -= t;
-        }
-        Amat[(size_t)n * NJ * 12 + idx] = v;
-    }
-}
-
 // ---- kernel B: per-vertex blend shapes + skinning + this tile's share of the joint regression ----------------------
 // Workgroup = 4 waves on the SAME 64 vertices and PB persons.  Each wave accumulates a quarter of the 207 pose-blend terms
 // (the only long dependent loop: strided posedirs loads), the partial sums meet in LDS, then wave w finishes persons
 // 4w .. 4w+3 (shape blend, skinning) and the workgroup reduces reg[r][tile] . vertex for the 26 regressors.
 // Workgroup id -> (tile, person group): ids that differ by 8 run on the same XCD, so the person groups of a tile get
 // consecutive slots of ONE XCD (posedirs tile: HBM once, then L2).
-constexpr int SKIN_WAVES = 4, KQ = (NPF + SKIN_WAVES - 1) / SKIN_WAVES;   // 52 terms per wave
-constexpr int PPW = PB / SKIN_WAVES;                                      // persons finished per wave
-constexpr int U_FLOATS = SKIN_WAVES * PB * 3 * 64;                        // blend partials, then the vertex tile
-constexpr int KC = 13, NCH = KQ / KC;                                     // posedirs terms per register chunk, chunks per wave
-static_assert(KQ == KC * NCH, "chunking of the pose-blend quarter");
-
-__device__ __forceinline__ void pd_load(float (&d)[KC][3], const float* __restrict__ pdv, int kbase) {
-#pragma unroll
-    for (int i = 0; i < KC; ++i) {
-        const size_t off = (size_t)min(kbase + i, NPF - 1) * (NV * 3);
-        d[i][0] = pdv[off]; d[i][1] = pdv[off + 1]; d[i][2] = pdv[off + 2];
-    }
-}
-
-__device__ __forceinline__ void pd_blend(f2 (&po)[PB / 2][3], const float (&d)[KC][3], const float (*s_pf)[PB], int kbase) {
-#pragma unroll
-    for (int i = 0; i < KC; ++i) {
-        const int k = kbase + i;
-        const bool in = k < NPF;                                  // the last quarter is one term short
-        const float d0 = in ? d[i][0] : 0.f, d1 = in ? d[i][1] : 0.f, d2 = in ? d[i][2] : 0.f;
-        const f2 dd0{d0, d0}, dd1{d1, d1}, dd2{d2, d2};
-        const float* row = s_pf[min(k, NPF - 1)];
-#pragma unroll
-        for (int p4 = 0; p4 < PB; p4 += 4) {
-            const float4 f = *reinterpret_cast<const float4*>(row + p4);
-            const f2 fa{f.x, f.y}, fb{f.z, f.w};
-            po[p4 / 2][0] = pk_fma(fa, dd0, po[p4 / 2][0]); po[p4 / 2][1] = pk_fma(fa, dd1, po[p4 / 2][1]); po[p4 / 2][2] = pk_fma(fa, dd2, po[p4 / 2][2]);
-            po[p4 / 2 + 1][0] = pk_fma(fb, dd0, po[p4 / 2 + 1][0]); po[p4 / 2 + 1][1] = pk_fma(fb, dd1, po[p4 / 2 + 1][1]); po[p4 / 2 + 1][2] = pk_fma(fb, dd2, po[p4 / 2 + 1][2]);
-        }
-    }
-}
-
 // Measured alternatives (N = 64, whole SMPL call): pose features and the relative transforms read through the scalar cache
 // as SGPR operands instead of LDS (no staging, one barrier less): 44 us against 37 us -- the s_load round trips cannot be
 // prefetched deep enough with ~100 SGPRs.
@@ -413,17 +282,6 @@ __global__ __launch_bounds__(256) void smpl_root_sub_kernel(float* __restrict__ 
 
 using namespace romp;
 
-struct smpl_ctx {
-    int nb = 10;
-    int cap = 0;
-    Parents par;
-    int* sched = nullptr;          // [n_levels, start[MAXLV + 1], order[NJ], parent[NJ]] for the pose kernel
-    float* jpart = nullptr;        // (cap, NT, NREG, 3) per-tile joint partial sums
-    float *vt = nullptr, *sd = nullptr, *pd = nullptr, *lbsw = nullptr, *reg = nullptr, *Jt = nullptr, *Js = nullptr;
-    int* pick = nullptr;
-    float *pose_feat = nullptr, *Amat = nullptr, *root = nullptr;
-};
-
 // `st`: the stream of the call that will use the buffers; the clear is ordered on it, ahead of that call's pose kernel
 static int smpl_reserve(smpl_ctx* c, int N, hipStream_t st) {
     if (N <= c->cap) return ROMP_OK;
@@ -564,6 +422,7 @@ void smpl_ctx_destroy(smpl_ctx* c) {
         if (p) hipFree(p);
     if (c->pick) hipFree(c->pick);
     if (c->sched) hipFree(c->sched);
+    smpl_grad_release(c);
     delete c;
 }
 

@@ -117,6 +117,7 @@ def load():
         'smpl_ctx_create': (C.c_int, [C.POINTER(vp), vp, vp, i32, vp, vp, vp, i64p, vp, vp, i64p, i32, vp]),
         'smpl_forward': (C.c_int, [vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         'smpl_ctx_destroy': (None, [vp]),
+        'smpl_backward': (C.c_int, [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
         'romp_preprocess': (C.c_int, [vp, i32, i32, vp, i32, C.POINTER(C.c_float), vp]),
         'romp_preprocess_batch': (C.c_int, [vp, i32, i32, i32, vp, i32, C.POINTER(C.c_float), vp]),
         'romp_bev_postprocess': (C.c_int, [vp, vp, vp, i32, vp, f, f, vp, vp, vp, vp, vp]),
@@ -167,6 +168,8 @@ EVAL_EXPORTS = ['romp_eval_match2d', 'romp_eval_points', 'romp_eval_accumulate']
 RH_EXPORTS = ['romp_rh_score', 'romp_rh_accumulate']
 # include/romp_hip_canvases.h: many canvases in one pass (frame batches, the mesh turntable)
 CANVAS_EXPORTS = ['romp_sim3dr_render_canvases', 'romp_view_turntable']
+# include/romp_hip_smpl_grad.h: the backward of the SMPL layer (gradients of betas and thetas)
+SMPL_GRAD_EXPORTS = ['smpl_backward']
 
 
 def has_bf16x3():

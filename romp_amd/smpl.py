@@ -4,6 +4,9 @@ Same constructor and call signature: ``SMPL(model_path, model_type='smpl')(betas
 root_align=False) -> (verts (N,6890,3), joints (N,71,3), faces)``.  The model file schema is
 the reference's packed ``.pth`` (pack_smpl_info.py:70-111).  PyTorch holds the buffers; the
 forward is ``smpl_forward`` of libromp_hip.so (csrc/smpl.hip).
+
+[romp_amd] The layer is differentiable in ``betas`` and ``poses``: when grad mode is on and one of them requires
+grad, the call goes through an autograd node whose backward is ``smpl_backward`` (csrc/smpl_grad.hip).
 """
 import ctypes as C
 
@@ -76,6 +79,16 @@ class SMPL(nn.Module):
         dev = self.shapedirs.device
         betas = betas.to(dev).float().contiguous()
         poses = poses.to(dev).float().contiguous()
+        if torch.is_grad_enabled() and (betas.requires_grad or poses.requires_grad):
+            # [romp_amd] the differentiable path (smpl_backward, include/romp_hip_smpl_grad.h); everything else, ROMP / BEV
+            # inference included, takes the lines below exactly as before
+            verts, joints = _SMPLFunction.apply(self, betas, poses, bool(root_align))
+            return verts, joints, self.faces_tensor
+        verts, joints = self._run_forward(betas, poses, root_align)
+        return verts, joints, self.faces_tensor
+
+    def _run_forward(self, betas, poses, root_align):
+        dev = self.shapedirs.device
         ctx = self._context()
         N = betas.shape[0]
         verts = torch.empty(N, 6890, 3, device=dev, dtype=torch.float32)
@@ -83,4 +96,34 @@ class SMPL(nn.Module):
         with torch.cuda.device(dev):
             L.check(L.load().smpl_forward(ctx, L.ptr(betas), int(betas.shape[1]), L.ptr(poses), N, int(bool(root_align)),
                                           L.ptr(verts), L.ptr(joints), L.stream_ptr(dev)))
-        return verts, joints, self.faces_tensor
+        return verts, joints
+
+
+class _SMPLFunction(torch.autograd.Function):
+    """smpl_forward / smpl_backward as one autograd node.  Saves only betas, poses and root_align: the backward
+    recomputes what it needs, so other forwards may run on the module in between."""
+
+    @staticmethod
+    def forward(ctx, module, betas, poses, root_align):
+        ctx.module, ctx.root_align = module, root_align
+        ctx.save_for_backward(betas, poses)
+        ctx.set_materialize_grads(False)                 # an output nobody used arrives as None -> NULL, not as zeros
+        verts, joints = module._run_forward(betas, poses, root_align)
+        return verts, joints
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_verts, grad_joints):
+        betas, poses = ctx.saved_tensors
+        module, dev = ctx.module, betas.device
+        need_b, need_p = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gv = None if grad_verts is None else grad_verts.to(dev).float().contiguous()
+        gj = None if grad_joints is None else grad_joints.to(dev).float().contiguous()
+        N = betas.shape[0]
+        gb = torch.empty_like(betas) if need_b else None
+        gp = torch.empty_like(poses) if need_p else None
+        if need_b or need_p:
+            with torch.cuda.device(dev):
+                L.check(L.load().smpl_backward(module._context(), L.ptr(betas), int(betas.shape[1]), L.ptr(poses), N,
+                                               int(ctx.root_align), L.ptr(gv), L.ptr(gj), L.ptr(gb), L.ptr(gp), L.stream_ptr(dev)))
+        return None, gb, gp, None
