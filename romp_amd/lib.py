@@ -45,6 +45,12 @@ class RompOp(C.Structure):
     ]
 
 
+class FitSegment(C.Structure):
+    """Mirror of `struct romp_fit_segment` (include/romp_hip_fit.h): one parameter tensor of a romp_fit_adam call."""
+    _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
+                ('prior_ref', C.c_void_p), ('prior_w', C.c_void_p), ('rows', C.c_int32), ('cols', C.c_int32)]
+
+
 _lib = None
 
 
@@ -134,6 +140,8 @@ def load():
                                                   i32, vp, vp, vp, vp]),
         'romp_view_turntable': (C.c_int, [vp, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, i32, i32, C.c_double,
                                           vp, vp, vp, vp]),
+        'romp_fit_reproject': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), i32, f, f, f, vp, vp, vp, vp, i32, vp]),
+        'romp_fit_adam': (C.c_int, [C.POINTER(FitSegment), i32, f, f, f, f, i32, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -170,6 +178,8 @@ RH_EXPORTS = ['romp_rh_score', 'romp_rh_accumulate']
 CANVAS_EXPORTS = ['romp_sim3dr_render_canvases', 'romp_view_turntable']
 # include/romp_hip_smpl_grad.h: the backward of the SMPL layer (gradients of betas and thetas)
 SMPL_GRAD_EXPORTS = ['smpl_backward']
+# include/romp_hip_fit.h: fitting to 2-D keypoints (the reprojection loss with its gradients, the Adam step of a whole fit)
+FIT_EXPORTS = ['romp_fit_reproject', 'romp_fit_adam']
 
 
 def has_bf16x3():
