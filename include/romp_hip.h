@@ -368,7 +368,9 @@ int  romp_preprocess_batch(const unsigned char* bgr_u8, int B, int H, int W, flo
 /* BEV per-image post-processing (bev/post_parser.py:68-136,167-222): camera translation, perspective
  * projection (normalised and original-image pixels), projection-based duplicate suppression, outlier
  * removal.  Persons of image b are rows offsets[b]..offsets[b+1]-1 (offsets: B+1 int32, device);
- * pad_info: (B,6) device.  keep[row] = 1 if the person survives. */
+ * pad_info: (B,6) device.  keep[row] = 1 if the person survives.  Suppression and outlier removal take the first 64
+ * rows of an image (the BEV parser's own cap): a row past them gets its cam_trans, pj2d and pj2d_org and keep = 0.
+ * Every row of every non-empty image is written; an empty image (offsets[b+1] == offsets[b]) writes nothing. */
 int  romp_bev_postprocess(const float* joints /* (N,71,3) */, const float* cam /* (N,3) */, const int32_t* offsets,
                           int B, const float* pad_info, float nms_thresh, float relative_scale_thresh,
                           float* pj2d, float* pj2d_org, float* cam_trans, int32_t* keep, void* stream);

@@ -30,6 +30,13 @@ __global__ void preprocess_kernel(const unsigned char* __restrict__ src_all, int
 
 constexpr int PJ = 71, PMAX = 64;
 
+// denormalize_cam_params_to_trans (:114-128) of one row: cam (scale, ty, tx) -> translation (x, y, depth)
+__device__ __forceinline__ void cam_to_trans(const float* __restrict__ c, float* t) {
+    const float tan_fov = 0.57735026918962573f;
+    const float depth = 1.f / (c[0] * tan_fov + 1e-3f);
+    t[0] = c[2] * depth * tan_fov; t[1] = c[1] * depth * tan_fov; t[2] = depth;
+}
+
 __global__ __launch_bounds__(256) void bev_post_kernel(const float* __restrict__ joints, const float* __restrict__ cam,
                                                         const int* __restrict__ offsets, const float* __restrict__ pad_info,
                                                         float nms_thresh, float rel_thresh, float scale_thresh,
@@ -38,29 +45,38 @@ __global__ __launch_bounds__(256) void bev_post_kernel(const float* __restrict__
     __shared__ float s_scale[PMAX], s_tr[PMAX][3], s_mean[PMAX];
     __shared__ int s_removed[PMAX], s_alive[PMAX], s_n_alive;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int off = offsets[b], n = min(offsets[b + 1] - off, PMAX);
+    // Suppression and outlier removal take the first PMAX rows of an image; rows past them get their per-row outputs
+    // (translation, projections) and keep = 0.
+    const int off = offsets[b], n_all = offsets[b + 1] - off, n = min(n_all, PMAX);
     if (n <= 0) return;
     const float* pi = pad_info + b * 6;                       // top, bottom, left, right, h, w
     const float top = pi[0], left = pi[2], pad_size = fmaxf(pi[4], pi[5]);
-    const float tan_fov = 0.57735026918962573f;
     if (tid < n) {                                            // denormalize_cam_params_to_trans (:114-128)
         const float* c = cam + (size_t)(off + tid) * 3;
-        const float depth = 1.f / (c[0] * tan_fov + 1e-3f);
-        s_tr[tid][0] = c[2] * depth * tan_fov; s_tr[tid][1] = c[1] * depth * tan_fov; s_tr[tid][2] = depth;
+        cam_to_trans(c, s_tr[tid]);
         for (int k = 0; k < 3; ++k) cam_trans[(size_t)(off + tid) * 3 + k] = s_tr[tid][k];
         s_scale[tid] = c[0] * 2.f;
         s_removed[tid] = 0;
     }
+    for (int r = PMAX + tid; r < n_all; r += 256) {           // rows past PMAX: translation only, never kept
+        float t[3];
+        cam_to_trans(cam + (size_t)(off + r) * 3, t);
+        for (int k = 0; k < 3; ++k) cam_trans[(size_t)(off + r) * 3 + k] = t[k];
+        keep[off + r] = 0;
+    }
     __syncthreads();
-    for (int i = tid; i < n * PJ; i += 256) {                  // perspective_projection (:68-107), then to org image
+    for (int i = tid; i < n_all * PJ; i += 256) {              // perspective_projection (:68-107), then to org image
         const int p = i / PJ;
         const float* j = joints + (size_t)(off * PJ + i) * 3;
-        const float z = (j[2] + s_tr[p][2]) + 1e-6f;
-        float x = (j[0] + s_tr[p][0]) / z * 443.4f, y = (j[1] + s_tr[p][1]) / z * 443.4f;
+        float t[3];
+        if (p < PMAX) { t[0] = s_tr[p][0]; t[1] = s_tr[p][1]; t[2] = s_tr[p][2]; }
+        else cam_to_trans(cam + (size_t)(off + p) * 3, t);
+        const float z = (j[2] + t[2]) + 1e-6f;
+        float x = (j[0] + t[0]) / z * 443.4f, y = (j[1] + t[1]) / z * 443.4f;
         x /= 256.f; y /= 256.f;                                // normalize: /= img_size/2
         pj2d[(size_t)(off * PJ + i) * 2] = x; pj2d[(size_t)(off * PJ + i) * 2 + 1] = y;
         x = (x + 1.f) * pad_size / 2.f - left; y = (y + 1.f) * pad_size / 2.f - top;
-        s_pj[i * 2] = x; s_pj[i * 2 + 1] = y;
+        if (p < PMAX) { s_pj[i * 2] = x; s_pj[i * 2 + 1] = y; }
         pj2d_org[(size_t)(off * PJ + i) * 2] = x; pj2d_org[(size_t)(off * PJ + i) * 2 + 1] = y;
     }
     __syncthreads();

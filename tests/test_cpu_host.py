@@ -295,6 +295,26 @@ def test_host_preprocess_fallback_matches_oracle():
     assert np.abs(w2.sum(1) - 2048).max() <= 1
 
 
+PREPROCESS_FRAMES = ((1, 1), (1, 7), (7, 1), (2, 3), (36, 53), (513, 512), (300, 9))
+PREPROCESS_SIZES = (512, 64, 37)
+
+
+@pytest.mark.parametrize('out_size', PREPROCESS_SIZES)
+@pytest.mark.parametrize('shape', PREPROCESS_FRAMES)
+def test_host_preprocess_fallback_matches_oracle_on_edge_geometry(shape, out_size):
+    """The frames and output sizes of tests/test_gpu_bev_post.py's pre-processing tests: cubic taps that all land on the
+    replicated border, a centred pad whose sides differ by one, a one-pixel pad, a strip that is mostly padding."""
+    from oracle import cv_resize_oracle as CV
+    from romp_amd.utils import img_preprocess
+    img = np.random.RandomState(shape[0] * 1000 + shape[1]).randint(0, 256, shape + (3,)).astype(np.uint8)
+    a, pa = CV.img_preprocess(img, out_size)
+    b, pb = img_preprocess(img, out_size)
+    assert a.shape == (1, out_size, out_size, 3) and np.array_equal(a, b.numpy()) and pa.tolist() == pb.tolist()
+    side = max(shape)
+    assert pa.tolist() == [(side - shape[0]) // 2, (side - shape[0]) // 2 + shape[0], (side - shape[1]) // 2,
+                           (side - shape[1]) // 2 + shape[1], shape[0], shape[1]]
+
+
 def test_translation_lsq_recovers_known_translation():
     from romp_amd.post_parser import estimate_translation_lsq
     rs = np.random.RandomState(1)
