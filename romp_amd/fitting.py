@@ -1,4 +1,5 @@
-"""[romp_amd] Fitting the SMPL layer to 2-D keypoints on the device (include/romp_hip_fit.h, csrc/fit.hip).
+"""[romp_amd] Fitting the SMPL layer to 2-D keypoints on the device (include/romp_hip_fit.h, csrc/fit.hip), with SMPLify's pose
+priors and 3-D joint targets as further terms (include/romp_hip_fit_priors.h, csrc/fit_priors.hip).
 
 The reference has no counterpart: it regresses the parameters and stops.  A ROMP / BEV result can be refined here against a
 detector's keypoints or annotations, with the project's own camera conventions:
@@ -16,6 +17,12 @@ rho(e) = e or, for sigma > 0, Geman-McClure sigma^2 e / (sigma^2 + e).  The visi
 reference's unsquared norm, which has no gradient at a perfect fit.  camera 'weak': cam = (s, c1, c2), u = s x + c1,
 v = s y + c2 (batch_orth_proj); 'perspective': cam = cam_trans, p = X + cam, u = p.x / (p.z + 1e-6) * focal / half
 (BEV's perspective_projection, as ``romp_bev_project_verts``).  Coordinates are the network's normalised frame (-1..1).
+
+  ``PosePrior``          SMPLify's Gaussian mixture over the body pose (MaxMixturePrior, loss_funcs/prior_loss.py:160-247).
+  ``pose_prior_loss``    autograd node around ``romp_fit_pose_prior``: the max-mixture term and the joint-angle prior.
+  ``joints3d_loss``      autograd node around ``romp_fit_joints3d``: the distance to 3-D targets under the rule of calc_mpjpe /
+                         align_by_parts (loss_funcs/keypoints_loss.py:64-82), squared and normalised as the 2-D term.
+``KeypointFitter`` takes all three as further terms of its objective, one launch each per step.
 """
 import ctypes as C
 
@@ -93,6 +100,163 @@ def reprojection_loss(joints, cam, kp2d, conf=None, joint_inds=None, sigma=0., c
     return _ReprojectFunction.apply(joints, cam, kp2d, conf, inds_c, _mode(camera), focal, half, sigma)
 
 
+class PosePrior(object):
+    """SMPLify's Gaussian-mixture pose prior as romp_fit_pose_prior reads it (include/romp_hip_fit_priors.h).
+
+    means (M,D), covars (M,D,D), weights (M,): the mixture over the body pose (D = 69 in SMPLify's gmm_08.pkl).  Built in
+    float64 as MaxMixturePrior builds it (prior_loss.py:202-212): precisions = inv(covars), made symmetric as (P + P^T) / 2,
+    nll_weights = weights / ((2 pi)^(69/2) * sqrtdet / min sqrtdet); kept as the float32 device tensors ``means`` (M,D),
+    ``precisions`` (M,D,D) and ``offsets`` (M,) = -log(nll_weights)."""
+
+    def __init__(self, means, covars, weights, device=None):
+        means, covars, weights = (np.asarray(torch.as_tensor(a).detach().cpu().numpy(), dtype=np.float64) for a in (means, covars, weights))
+        if means.ndim != 2 or covars.shape != (means.shape[0], means.shape[1], means.shape[1]) or weights.shape != (means.shape[0],):
+            raise ValueError('PosePrior: means (M,D), covars (M,D,D), weights (M,)')
+        if not 1 <= means.shape[1] <= 69 or not 1 <= means.shape[0] <= 16:
+            raise ValueError('PosePrior: 1 <= D <= 69 and 1 <= M <= 16, got D %d, M %d' % (means.shape[1], means.shape[0]))
+        prec = np.stack([np.linalg.inv(c) for c in covars])
+        prec = 0.5 * (prec + prec.transpose(0, 2, 1))
+        sqrdets = np.array([np.sqrt(np.linalg.det(c)) for c in covars])
+        nll_weights = weights / ((2 * np.pi) ** (69 / 2.) * (sqrdets / sqrdets.min()))
+        self._set(torch.from_numpy(means), torch.from_numpy(prec), torch.from_numpy(-np.log(nll_weights)), device)
+
+    def _set(self, means, precisions, offsets, device):
+        dev = torch.device('cpu' if device is None else device)
+        self.means, self.precisions, self.offsets = (_f32(t, dev) for t in (means, precisions, offsets))
+        return self
+
+    @classmethod
+    def from_file(cls, path, device=None):
+        """SMPLify's gmm_XX.pkl (a pickled dict with means, covars, weights; latin1 encoding) or an .npz with the same keys."""
+        gmm = np.load(path, allow_pickle=True, encoding='latin1')    # numpy unpickles what is neither .npy nor .npz
+        return cls(gmm['means'], gmm['covars'], gmm['weights'], device)
+
+    def to(self, device):
+        return PosePrior.__new__(PosePrior)._set(self.means, self.precisions, self.offsets, device)
+
+    def sliced(self, D):
+        """The prior of the first D pose parameters: means[:, :D] and precisions[:, :D, :D], as merged_log_likelihood slices
+        them for a shorter pose (prior_loss.py:233-237)."""
+        return PosePrior.__new__(PosePrior)._set(self.means[:, :D], self.precisions[:, :D, :D], self.offsets, self.means.device)
+
+
+def _pose_prior(poses, prior, w_gmm, w_angle, loss, best, gp, accumulate, history=None, row=0):
+    dev = poses.device
+    if dev.type != 'cuda':
+        raise L.RompHipError('the pose prior runs on the HIP device only (no CPU fallback); move the tensors to "cuda:N"')
+    M, D = (0, 69) if prior is None else prior.means.shape
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_fit_pose_prior(L.ptr(poses), poses.shape[0], L.ptr(None if prior is None else prior.means),
+                                             L.ptr(None if prior is None else prior.precisions),
+                                             L.ptr(None if prior is None else prior.offsets), M, D, float(w_gmm), float(w_angle),
+                                             L.ptr(loss), L.ptr(best), L.ptr(gp), int(accumulate), L.ptr(history), int(row),
+                                             L.stream_ptr(dev)))
+
+
+def _joints3d(joints, trans, targets, conf, inds_c, align_c, sigma, weight, loss, gj, gt, accumulate, history=None, row=0):
+    dev = joints.device
+    if dev.type != 'cuda':
+        raise L.RompHipError('the 3-D joint loss runs on the HIP device only (no CPU fallback); move the tensors to "cuda:N"')
+    N, J = joints.shape[:2]
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_fit_joints3d(L.ptr(joints), N, J, L.ptr(trans), L.ptr(targets), L.ptr(conf), targets.shape[1], inds_c,
+                                           align_c, 0 if align_c is None else len(align_c), float(sigma), float(weight), L.ptr(loss),
+                                           L.ptr(gj), L.ptr(gt), int(accumulate), L.ptr(history), int(row), L.stream_ptr(dev)))
+
+
+def _align(align_inds):
+    """-> ctypes int32 array of the alignment keypoints, or None.  The C side checks range and repeats."""
+    if align_inds is None:
+        return None
+    idx = [int(i) for i in (align_inds.tolist() if hasattr(align_inds, 'tolist') else align_inds)]
+    return (C.c_int32 * len(idx))(*idx) if idx else None
+
+
+def _prior_on(prior, dev):
+    """The prior's tensors on the device of the fit, contiguous."""
+    if prior is None:
+        return None
+    if not isinstance(prior, PosePrior):
+        raise ValueError('pose_prior must be a romp_amd.fitting.PosePrior')
+    return prior.to(dev)
+
+
+class _PosePriorFunction(torch.autograd.Function):
+    """romp_fit_pose_prior as an autograd node.  The two losses have gradients of their own, so the forward launches once per
+    term (the angle term with the mixture off) and leaves both; the backward scales them."""
+
+    @staticmethod
+    def forward(ctx, poses, prior):
+        N = poses.shape[0]
+        loss = torch.zeros(N, 2, device=poses.device, dtype=torch.float32)
+        g_angle = torch.empty_like(poses)
+        _pose_prior(poses, None, 0., 1., loss, None, g_angle, 0)
+        gmm, g_gmm = loss[:, 0], None                                # zeros without a mixture
+        if prior is not None:
+            both, g_gmm = torch.empty_like(loss), torch.empty_like(poses)
+            _pose_prior(poses, prior, 1., 0., both, None, g_gmm, 0)
+            gmm = both[:, 0]
+        ctx.has_gmm = g_gmm is not None
+        ctx.save_for_backward(*([g_angle, g_gmm] if ctx.has_gmm else [g_angle]))
+        return gmm.clone(), loss[:, 1].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_gmm, grad_angle):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        g = ctx.saved_tensors[0] * grad_angle.to(ctx.saved_tensors[0].device).float()[:, None]
+        if ctx.has_gmm:
+            g = g + ctx.saved_tensors[1] * grad_gmm.to(g.device).float()[:, None]
+        return g, None
+
+
+def pose_prior_loss(poses, prior=None):
+    """poses (N,72), prior: a ``PosePrior`` or None (mixture off) -> (gmm (N,), angle (N,)), both unweighted and differentiable
+    in poses: the max-mixture negative log-likelihood of poses[:, 3:3+D] and the joint-angle prior of the elbows and knees."""
+    dev = poses.device
+    poses = _f32(poses, dev)
+    if poses.dim() != 2 or poses.shape[1] != 72:
+        raise ValueError('pose_prior_loss: poses (N,72)')
+    return _PosePriorFunction.apply(poses, _prior_on(prior, dev))
+
+
+class _Joints3dFunction(torch.autograd.Function):
+    """romp_fit_joints3d as an autograd node: the forward launch leaves both gradients, the backward scales them."""
+
+    @staticmethod
+    def forward(ctx, joints, trans, targets, conf, inds_c, align_c, sigma):
+        loss = torch.empty(joints.shape[0], device=joints.device, dtype=torch.float32)
+        gj, gt = torch.empty_like(joints), None if trans is None else torch.empty_like(trans)
+        _joints3d(joints, trans, targets, conf, inds_c, align_c, sigma, 1., loss, gj, gt, 0)
+        ctx.has_trans = gt is not None
+        ctx.save_for_backward(*([gj, gt] if ctx.has_trans else [gj]))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        gj = ctx.saved_tensors[0]
+        g = grad_loss.to(gj.device).float()
+        need_j, need_t = ctx.needs_input_grad[0], ctx.has_trans and ctx.needs_input_grad[1]
+        return (gj * g[:, None, None] if need_j else None, ctx.saved_tensors[1] * g[:, None] if need_t else None,
+                None, None, None, None, None)
+
+
+def joints3d_loss(joints, targets, conf=None, joint_inds=None, align_inds=None, sigma=0., trans=None):
+    """joints (N,J,3), targets (N,K,3) in the frame of the joints (plus trans (N,3) when given), conf (N,K) or None, joint_inds:
+    K distinct joint indices or None (= the first K joints), align_inds: indices into the K keypoints whose mean is taken off
+    predictions and targets alike, or None -> loss (N,), differentiable in joints and trans."""
+    dev = joints.device
+    joints, targets = _f32(joints, dev), _f32(targets, dev)
+    conf = None if conf is None else _f32(conf, dev)
+    trans = None if trans is None else _f32(trans, dev)
+    if joints.dim() != 3 or joints.shape[2] != 3 or targets.dim() != 3 or targets.shape[0] != joints.shape[0] or targets.shape[2] != 3 or \
+            (conf is not None and conf.shape != targets.shape[:2]) or (trans is not None and trans.shape != (joints.shape[0], 3)):
+        raise ValueError('joints3d_loss: joints (N,J,3), targets (N,K,3), conf (N,K), trans (N,3)')
+    return _Joints3dFunction.apply(joints, trans, targets, conf, _inds(joint_inds, targets.shape[1]), _align(align_inds), sigma)
+
+
 class KeypointFitter(object):
     """Adam on (betas, poses, cam) against 2-D keypoints, every step on the device:
 
@@ -102,16 +266,29 @@ class KeypointFitter(object):
     smpl: a ``romp_amd.smpl.SMPL`` on the device.  The priors are L2 with per-column weights, added to the gradient inside the
     Adam launch:  w_betas |betas|^2  keeps the shape small,  w_pose |poses - poses0|^2  holds the pose near the start, the
     global orientation (columns 0-2) excepted.  Each weight is a number or a vector with one entry per column.
-    ``loss_history`` (steps + 1, N) holds the data term before every step and after the last; it stays on the device."""
+    ``loss_history`` (steps + 1, N) holds the 2-D data term before every step and after the last; it stays on the device.
+
+    SMPLify's terms (include/romp_hip_fit_priors.h), all off by default, each one more launch per step:
+    ``pose_prior`` (a ``PosePrior``) with ``w_gmm`` > 0 adds  w_gmm * min_m (0.5 d^T P_m d + offset_m)  over the body pose;
+    ``w_angle`` > 0 adds  w_angle * sum exp(2 s theta)  over elbows and knees; both come with ``prior_history``
+    (steps + 1, N, 2), unweighted.  ``joints3d`` (N,K,3) given to ``fit`` adds  w_3d * (the loss of ``joints3d_loss``)  with
+    ``sigma_3d`` and ``align_inds``, and ``loss3d_history`` (steps + 1, N), unweighted.  With the perspective camera the targets
+    are camera-space points (the joints plus cam); with the weak camera they are in the frame of the joints.  ``kp2d`` may be
+    None when ``joints3d`` is given: the 2-D launch is skipped and ``loss_history`` is zeros."""
 
     def __init__(self, smpl, camera='weak', steps=30, lr=0.02, sigma=0., w_betas=1e-4, w_pose=1e-4, root_align=False,
-                 focal=443.4, half=256., betas=(0.9, 0.999), eps=1e-8):
+                 focal=443.4, half=256., betas=(0.9, 0.999), eps=1e-8, pose_prior=None, w_gmm=0., w_angle=0., w_3d=1., sigma_3d=0.,
+                 align_inds=None):
         self.smpl, self.camera, self.mode = smpl, camera, _mode(camera)
         self.steps, self.lr, self.sigma = int(steps), float(lr), float(sigma)
         self.w_betas, self.w_pose, self.root_align = w_betas, w_pose, bool(root_align)
         self.focal, self.half, self.adam_betas, self.eps = float(focal), float(half), (float(betas[0]), float(betas[1])), float(eps)
+        self.pose_prior, self.w_gmm, self.w_angle = pose_prior, float(w_gmm), float(w_angle)
+        self.w_3d, self.sigma_3d, self.align_inds = float(w_3d), float(sigma_3d), align_inds
         if self.steps < 0:
             raise ValueError('steps must not be negative')
+        if self.w_gmm < 0 or self.w_angle < 0 or self.w_3d < 0:
+            raise ValueError('w_gmm, w_angle and w_3d must not be negative')
 
     @staticmethod
     def _weights(w, cols, dev, free=0):
@@ -127,47 +304,80 @@ class KeypointFitter(object):
             raise ValueError('a prior weight vector needs %d entries, got %d' % (cols, out.numel()))
         return out
 
-    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None):
+    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None):
         """The buffers of one fit and its two halves of a step (``_FitRun``); ``fit`` drives it."""
-        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds)
+        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d)
 
-    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None):
+    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None):
         """betas0 (N,n_betas), poses0 (N,72), cam0 (N,3) (`cam` or `cam_trans`, by the camera), kp2d (N,K,2) in the normalised
-        frame, conf (N,K) or None, joint_inds: K joint indices of the 71 or None (= the first K).  The inputs are not changed.
-        -> dict(betas, poses, cam, verts, joints, loss_history (steps + 1, N)), device tensors; nothing is downloaded."""
-        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds)
+        frame (None: no 2-D term, joints3d is needed then), conf (N,K) or None, joint_inds: K joint indices of the 71 or None
+        (= the first K); joints3d (N,K3,3) or None, conf3d (N,K3) or None, joint_inds3d likewise.  The inputs are not changed.
+        -> dict(betas, poses, cam, verts, joints, loss_history (steps + 1, N)), device tensors; nothing is downloaded; with the
+        prior terms on also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N)."""
+        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d)
         for s in range(self.steps):
             run.evaluate(s)
             run.update(s + 1)
         run.evaluate(self.steps)
-        return {'betas': run.betas, 'poses': run.poses, 'cam': run.cam, 'verts': run.verts, 'joints': run.joints,
-                'loss_history': run.history}
+        run.prior(self.steps, accumulate=0)                           # the prior's last row; its gradient is not used
+        out = {'betas': run.betas, 'poses': run.poses, 'cam': run.cam, 'verts': run.verts, 'joints': run.joints,
+               'loss_history': run.history}
+        if run.prior_on:
+            out['prior_history'] = run.prior_history
+        if run.targets3d is not None:
+            out['loss3d_history'] = run.history3d
+        return out
 
 
 class _FitRun(object):
     """Device buffers of one KeypointFitter.fit and the two halves of a step.  evaluate(row): smpl_forward and
     romp_fit_reproject (loss into history[row], joint and camera gradients); update(step): smpl_backward from the joint
-    gradients alone and romp_fit_adam over betas, poses and cam (step counts from 1)."""
+    gradients alone and romp_fit_adam over betas, poses and cam (step counts from 1).  With 3-D targets evaluate also runs
+    romp_fit_joints3d onto the same gradients; with a prior term on update runs romp_fit_pose_prior between its two launches
+    (losses into prior_history[the row of the last evaluate])."""
 
-    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds):
+    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d=None, conf3d=None, joint_inds3d=None):
         self.fitter, smpl = fitter, fitter.smpl
         self.dev = dev = smpl.shapedirs.device
         self.ctx = smpl._context()                                   # raises without a HIP device
         self.h = L.load()
         self.betas, self.poses, self.cam = (_f32(t, dev).detach().clone() for t in (betas0, poses0, cam0))
-        self.kp2d = _f32(kp2d, dev)
-        self.conf = None if conf is None else _f32(conf, dev)
+        if kp2d is None and joints3d is None:
+            raise ValueError('fit: kp2d or joints3d is needed')
+        self.kp2d = None if kp2d is None else _f32(kp2d, dev)
+        self.conf = None if conf is None or kp2d is None else _f32(conf, dev)
         N, nb = self.betas.shape
-        if self.poses.shape != (N, 72) or self.cam.shape != (N, 3) or self.kp2d.dim() != 3 or self.kp2d.shape[0] != N or \
-                self.kp2d.shape[2] != 2 or (self.conf is not None and self.conf.shape != self.kp2d.shape[:2]):
+        if self.poses.shape != (N, 72) or self.cam.shape != (N, 3) or (self.kp2d is not None and (
+                self.kp2d.dim() != 3 or self.kp2d.shape[0] != N or self.kp2d.shape[2] != 2 or
+                (self.conf is not None and self.conf.shape != self.kp2d.shape[:2]))):
             raise ValueError('fit: betas (N,n_betas), poses (N,72), cam (N,3), kp2d (N,K,2), conf (N,K)')
         self.N, self.nb = N, nb
-        self.inds_c = _inds(joint_inds, self.kp2d.shape[1])
+        self.inds_c = None if self.kp2d is None else _inds(joint_inds, self.kp2d.shape[1])
         f32 = dict(device=dev, dtype=torch.float32)
         self.verts, self.joints = torch.empty(N, 6890, 3, **f32), torch.empty(N, 71, 3, **f32)
-        self.loss, self.gj, self.gc = torch.empty(N, **f32), torch.empty(N, 71, 3, **f32), torch.empty(N, 3, **f32)
+        self.loss, self.gj = torch.empty(N, **f32), torch.empty(N, 71, 3, **f32)
+        # without a 2-D term nothing writes the gradient of a weak camera: it is zero, and Adam leaves the camera where it is
+        self.gc = torch.empty(N, 3, **f32) if self.kp2d is not None else torch.zeros(N, 3, **f32)
         self.gb, self.gp = torch.empty_like(self.betas), torch.empty_like(self.poses)
-        self.history = torch.empty(fitter.steps + 1, N, **f32)
+        self.history = torch.empty(fitter.steps + 1, N, **f32) if self.kp2d is not None else torch.zeros(fitter.steps + 1, N, **f32)
+        self.targets3d = self.conf3d = self.inds3d_c = self.align_c = self.history3d = None
+        if joints3d is not None:
+            self.targets3d = _f32(joints3d, dev)
+            self.conf3d = None if conf3d is None else _f32(conf3d, dev)
+            if self.targets3d.dim() != 3 or self.targets3d.shape[0] != N or self.targets3d.shape[2] != 3 or \
+                    (self.conf3d is not None and self.conf3d.shape != self.targets3d.shape[:2]):
+                raise ValueError('fit: joints3d (N,K,3), conf3d (N,K)')
+            self.inds3d_c, self.align_c = _inds(joint_inds3d, self.targets3d.shape[1]), _align(fitter.align_inds)
+            self.loss3d, self.history3d = torch.empty(N, **f32), torch.empty(fitter.steps + 1, N, **f32)
+        self.pose_prior = _prior_on(fitter.pose_prior, dev) if fitter.w_gmm > 0 else None
+        self.prior_on = self.pose_prior is not None or fitter.w_angle > 0
+        if self.prior_on:
+            self.loss_prior, self.prior_history = torch.empty(N, 2, **f32), torch.empty(fitter.steps + 1, N, 2, **f32)
+        self.row = 0
+        # A step is bound by the host issuing its launches, so a fit with nothing but the old four entries keeps the old two
+        # methods, test for test (profiles/fit_prior_latency.txt holds that step against the parent commit's).
+        if self.kp2d is not None and self.targets3d is None and not self.prior_on:
+            self.evaluate, self.update = self._evaluate_2d, self._update_2d
         self.state = torch.zeros(2, N * (nb + 72 + 3), **f32)        # Adam's m and v of the three tensors
         self.poses_ref = self.poses.clone()
         self.wb = fitter._weights(fitter.w_betas, nb, dev)
@@ -182,7 +392,7 @@ class _FitRun(object):
                                         None if ref is None or w is None else ref.data_ptr(), None if w is None else w.data_ptr(),
                                         N, p.shape[1])
 
-    def evaluate(self, row):
+    def _evaluate_2d(self, row):
         f, ra = self.fitter, int(self.fitter.root_align)
         with torch.cuda.device(self.dev):
             L.check(self.h.smpl_forward(self.ctx, L.ptr(self.betas), self.nb, L.ptr(self.poses), self.N, ra, L.ptr(self.verts),
@@ -190,13 +400,45 @@ class _FitRun(object):
         _reproject(self.joints, self.cam, self.kp2d, self.conf, self.inds_c, f.mode, f.focal, f.half, f.sigma, self.loss, self.gj,
                    self.gc, self.history, row)
 
-    def update(self, step):
+    def _update_2d(self, step):
         f, ra = self.fitter, int(self.fitter.root_align)
         with torch.cuda.device(self.dev):
             st = L.stream_ptr(self.dev)
             L.check(self.h.smpl_backward(self.ctx, L.ptr(self.betas), self.nb, L.ptr(self.poses), self.N, ra, None, L.ptr(self.gj),
                                          L.ptr(self.gb), L.ptr(self.gp), st))
             L.check(self.h.romp_fit_adam(self.segs, 3, f.lr, f.adam_betas[0], f.adam_betas[1], f.eps, int(step), st))
+
+    def evaluate(self, row):
+        f = self.fitter
+        if self.kp2d is not None:
+            self._evaluate_2d(row)
+        else:
+            with torch.cuda.device(self.dev):
+                L.check(self.h.smpl_forward(self.ctx, L.ptr(self.betas), self.nb, L.ptr(self.poses), self.N, int(f.root_align),
+                                            L.ptr(self.verts), L.ptr(self.joints), L.stream_ptr(self.dev)))
+        if self.targets3d is not None:                               # perspective: camera-space targets, trans = cam
+            cam = f.mode == 1
+            _joints3d(self.joints, self.cam if cam else None, self.targets3d, self.conf3d, self.inds3d_c, self.align_c, f.sigma_3d,
+                      f.w_3d, self.loss3d, self.gj, self.gc if cam else None, int(self.kp2d is not None), self.history3d, row)
+        self.row = row
+
+    def update(self, step):
+        f, ra = self.fitter, int(self.fitter.root_align)
+        with torch.cuda.device(self.dev):
+            st = L.stream_ptr(self.dev)
+            L.check(self.h.smpl_backward(self.ctx, L.ptr(self.betas), self.nb, L.ptr(self.poses), self.N, ra, None, L.ptr(self.gj),
+                                         L.ptr(self.gb), L.ptr(self.gp), st))
+            if self.prior_on:
+                self.prior(self.row, accumulate=1)
+            L.check(self.h.romp_fit_adam(self.segs, 3, f.lr, f.adam_betas[0], f.adam_betas[1], f.eps, int(step), st))
+
+    def prior(self, row, accumulate):
+        """romp_fit_pose_prior on the current poses: the losses into prior_history[row], the gradient into (or onto) that of the
+        poses.  Nothing when both prior terms are off."""
+        if self.prior_on:
+            f = self.fitter
+            _pose_prior(self.poses, self.pose_prior, f.w_gmm, f.w_angle, self.loss_prior, None, self.gp, accumulate,
+                        self.prior_history, row)
 
 
 def keypoints_to_input_frame(kp2d_org, pad_info):
@@ -208,19 +450,24 @@ def keypoints_to_input_frame(kp2d_org, pad_info):
     return (kp2d_org + off) * (2. / size) - 1.
 
 
-def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_info=None, **fit_args):
+def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_info=None, joints3d=None, conf3d=None, joint_inds3d=None,
+                   **fit_args):
     """Refine the result dict of a ``ROMP`` / ``BEV`` forward against keypoints in original-image pixels.
 
     outputs: the dict of ``forward`` / ``forward_batch`` (numpy arrays or tensors) with smpl_betas, smpl_thetas and cam
     (ROMP) or cam_trans (BEV); kp2d_org (N,K,2), conf (N,K) or None, row for row with the dict's persons (matching detections
     to annotations is the caller's job: ``evaluation.match_2d_greedy``).  pad_info: the (top, bottom, left, right, h, w) of the
-    frame's pre-processing; None means a 512 x 512 frame without padding.  fit_args go to ``KeypointFitter``.
+    frame's pre-processing; None means a 512 x 512 frame without padding.  fit_args go to ``KeypointFitter``, its pose_prior,
+    w_gmm, w_angle, w_3d, sigma_3d and align_inds among them.  joints3d (N,K3,3), conf3d (N,K3), joint_inds3d: 3-D targets, in
+    the frame of the joints for ROMP and in camera space (joints + cam_trans) for BEV; kp2d_org may be None then.
 
     ROMP is fitted with the weak-perspective camera `cam`; BEV with the perspective camera `cam_trans`, always root-aligned,
     infants (betas[:, 10] > 0.8) on the SMIL layer as in BEV's own parser (one host read of that mask, as there); BEV's `cam`
-    stays the network's.  Returns a copy of
+    stays the network's; the mixture prior describes adults, so the infants are fitted without it (their prior_history[..., 0]
+    is zero) and keep the angle prior.  Returns a copy of
     the dict, device tensors, with smpl_thetas, smpl_betas, cam / cam_trans, verts, joints, pj2d, pj2d_org rewritten (by
-    ``romp_project`` / ``romp_bev_project_verts``) and fit_loss (N,2): the loss before and after."""
+    ``romp_project`` / ``romp_bev_project_verts``) and fit_loss (N,2): the 2-D loss before and after; with a prior term on
+    also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N)."""
     from .post_parser import body_mesh_projection2image
     parser = getattr(model, 'smpl_parser', None)
     if parser is None:
@@ -229,17 +476,20 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
     dev = model.tdevice
     pad = [0., 512., 0., 512., 512., 512.] if pad_info is None else [float(v) for v in np.asarray(pad_info).reshape(-1)]
     betas, thetas = _f32(outputs['smpl_betas'], dev), _f32(outputs['smpl_thetas'], dev)
-    kp = keypoints_to_input_frame(_f32(kp2d_org, dev), pad)
+    kp = None if kp2d_org is None else keypoints_to_input_frame(_f32(kp2d_org, dev), pad)
     conf = None if conf is None else _f32(conf, dev)
+    joints3d, conf3d = (None if t is None else _f32(t, dev) for t in (joints3d, conf3d))
+    extra = ('prior_history', 'loss3d_history')
     N = betas.shape[0]
     out = dict(outputs)
     if not is_bev:
         fitter = KeypointFitter(parser.smpl_model, camera='weak', **dict(dict(root_align=model.settings.root_align), **fit_args))
-        res = fitter.fit(betas, thetas, _f32(outputs['cam'], dev), kp, conf, joint_inds)
+        res = fitter.fit(betas, thetas, _f32(outputs['cam'], dev), kp, conf, joint_inds, joints3d, conf3d, joint_inds3d)
         proj = body_mesh_projection2image(res['joints'], res['cam'], input2org_offsets=pad)
         out.update({'smpl_betas': res['betas'], 'smpl_thetas': res['poses'], 'cam': res['cam'], 'cam_trans': proj['cam_trans'],
                     'verts': res['verts'], 'joints': res['joints'], 'pj2d': proj['pj2d'], 'pj2d_org': proj['pj2d_org'],
                     'fit_loss': res['loss_history'][[0, -1]].t().contiguous()})
+        out.update({k: res[k] for k in extra if k in res})
         return out
     trans = _f32(outputs['cam_trans'], dev)
     args = dict(dict(root_align=True), **fit_args)
@@ -250,13 +500,21 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
     new = {'smpl_betas': betas.clone(), 'smpl_thetas': thetas.clone(), 'cam_trans': trans.clone(),
            'verts': torch.empty(N, 6890, 3, device=dev), 'joints': torch.empty(N, 71, 3, device=dev),
            'fit_loss': torch.empty(N, 2, device=dev)}
+    pick = lambda t, rows: None if t is None else t[rows]
     for layer, rows, nb in groups:
         if rows.numel() == 0:
             continue
         rows = rows.to(dev)
-        res = KeypointFitter(layer, camera='perspective', **args).fit(betas[rows][:, :nb], thetas[rows], trans[rows], kp[rows],
-                                                                      None if conf is None else conf[rows], joint_inds)
+        group_args = dict(args, pose_prior=None) if layer is parser.smil_model else args
+        res = KeypointFitter(layer, camera='perspective', **group_args).fit(
+            betas[rows][:, :nb], thetas[rows], trans[rows], pick(kp, rows), pick(conf, rows), joint_inds, pick(joints3d, rows),
+            pick(conf3d, rows), joint_inds3d)
         new['smpl_betas'][rows, :nb] = res['betas']
+        for key in extra:                                             # (steps + 1, n, ...) of this group into (steps + 1, N, ...)
+            if key in res:
+                if key not in new:
+                    new[key] = torch.zeros((res[key].shape[0], N) + tuple(res[key].shape[2:]), device=dev)
+                new[key][:, rows] = res[key]
         for key, val in (('smpl_thetas', res['poses']), ('cam_trans', res['cam']), ('verts', res['verts']), ('joints', res['joints']),
                          ('fit_loss', res['loss_history'][[0, -1]].t())):
             new[key][rows] = val

@@ -142,6 +142,9 @@ def load():
                                           vp, vp, vp, vp]),
         'romp_fit_reproject': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), i32, f, f, f, vp, vp, vp, vp, i32, vp]),
         'romp_fit_adam': (C.c_int, [C.POINTER(FitSegment), i32, f, f, f, f, i32, vp]),
+        'romp_fit_pose_prior': (C.c_int, [vp, i32, vp, vp, vp, i32, i32, f, f, vp, vp, vp, i32, vp, i32, vp]),
+        'romp_fit_joints3d': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, f, f, vp, vp, vp,
+                                        i32, vp, i32, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -180,6 +183,8 @@ CANVAS_EXPORTS = ['romp_sim3dr_render_canvases', 'romp_view_turntable']
 SMPL_GRAD_EXPORTS = ['smpl_backward']
 # include/romp_hip_fit.h: fitting to 2-D keypoints (the reprojection loss with its gradients, the Adam step of a whole fit)
 FIT_EXPORTS = ['romp_fit_reproject', 'romp_fit_adam']
+# include/romp_hip_fit_priors.h: SMPLify's pose priors (max-mixture GMM, joint angles) and 3-D joint targets for the same fit
+FIT_PRIOR_EXPORTS = ['romp_fit_pose_prior', 'romp_fit_joints3d']
 
 
 def has_bf16x3():
