@@ -34,9 +34,7 @@ def cam3dmap_anchor(fov=60.0, size=MAP):
 
 def _host_floats(P: Program, values):
     """Small constant table kept alive on the HOST (passed to the kernel by value at launch)."""
-    arr = (C.c_float * len(values))(*[float(v) for v in values])
-    P.consts.append(arr)
-    return C.cast(arr, C.c_void_p).value
+    return C.addressof(P.keep((C.c_float * len(values))(*[float(v) for v in values])))
 
 
 def build_bev_hrnet32(sd, device, input_size=512, bf16x3=False, split_k_items=0) -> Program:
@@ -87,7 +85,7 @@ def build_bev_hrnet32(sd, device, input_size=512, bf16x3=False, split_k_items=0)
     op = RompOp()
     op.kind, op.in_buf, op.res_buf, op.out_buf = OP_BEV_PACK, maps_fv.buf, f.buf, packed.buf
     op.in_cstride, op.res_cstride = maps_fv.cstride, f.cstride
-    P.ops.append(op); P.names.append('bev.pack'); P.flops.append(0.0); P.bytes.append(4.0 * 2 * 20 * MAP * MAP)
+    P.emit(op, 'bev.pack', 0.0, 4.0 * 2 * 20 * MAP * MAP)
     P.free(f)
     # ---- bv_out_layers: 3 x BasicBlock_1D = 6 x (Conv1d k3 + BN1d + ReLU), no residual (bev/model.py:24-45,179-182)
     h = packed
@@ -106,7 +104,7 @@ def build_bev_hrnet32(sd, device, input_size=512, bf16x3=False, split_k_items=0)
     op.in_cstride, op.res_cstride = maps_fv.cstride, h.cstride
     op.term_buf[0] = cam.buf
     op.weight = _host_floats(P, cam3dmap_anchor(60, MAP))
-    P.ops.append(op); P.names.append('bev.maps'); P.flops.append(float(VOX)); P.bytes.append(4.0 * 4 * VOX)
+    P.emit(op, 'bev.maps', float(VOX), 4.0 * 4 * VOX)
     P.free(h)
     P.free(maps_fv)
 
@@ -122,8 +120,7 @@ def build_bev_hrnet32(sd, device, input_size=512, bf16x3=False, split_k_items=0)
         o.relu = int(relu)
         o.weight = _host_floats(P, w.reshape(-1).tolist())
         o.scale, o.shift = _host_floats(P, s.tolist()), _host_floats(P, b.tolist())
-        P.ops.append(o); P.names.append(name); P.flops.append(2.0 * VOX * ch * ch * 27)
-        P.bytes.append(4.0 * VOX * ch * (3 if res is not None else 2))
+        P.emit(o, name, 2.0 * VOX * ch * ch * 27, 4.0 * VOX * ch * (3 if res is not None else 2))
         return out
 
     t1 = conv3d('bev.center_refine.conv1', c3, 'center_map_refiner', 'conv1', 'bn1', 1, True, None, None)

@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import warnings
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -173,6 +175,63 @@ def decode_h2(t, act_shift=ACT_SHIFT):
     return ((h[..., 0, :] + h[..., 1, :]) * (2.0 ** -act_shift)).reshape(t.shape)
 
 
+MARKERS = (OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT)              # stream control: no launch, no tensor
+FUSED_PAIRS = (OP_BBLOCK32, OP_BBLOCK64, OP_SEAM1X1)          # the NOP before such an op holds the pair's first conv
+
+
+def op_tensors(P, i):
+    """-> (reads, writes): the arena buffers (>= 0) the launch of op i reads and writes, for every op kind before and after the
+    fusion passes -- the ONE place that knows it (the format pass, the liveness query of the fusion passes and the race check all
+    ask here).  Whole buffers, channel slices ignored.  A fused pair is charged with both convs' operands (the intermediate tensor
+    included, which stays on chip: conservative)."""
+    ops = P.ops
+    op = ops[i]
+    if op.kind in MARKERS or op.kind == OP_NOP:
+        return [], []
+    if op.kind == OP_STEM2:                                  # reads the caller's image only (its in_buf names the tensor that no longer exists)
+        r, w = [], [op.out_buf]
+    elif op.kind in FUSED_PAIRS:
+        a = ops[i - 1]
+        # OPF_SEAM_DS: the folded downsample conv (two ops back) is computed from ITS input, its output -- the first conv's residual -- never materialises
+        r = [ops[i - 2].in_buf if op.kind == OP_SEAM1X1 and (op.flags & OPF_SEAM_DS) else a.res_buf, a.in_buf, op.in_buf, op.res_buf]
+        w = [a.out_buf, op.out_buf]
+    else:
+        r, w = [op.in_buf, op.res_buf], [op.out_buf]
+        if op.kind in (OP_FUSESUM, OP_FUSEUP):
+            r += op.term_buf[:op.n_terms]
+        elif op.kind == OP_BEV_MAPS:                         # a second output
+            w.append(op.term_buf[0])
+    return [b for b in r if b >= 0], [b for b in w if b >= 0]
+
+
+def read_elsewhere(P, i, buf, but=()):
+    """Does the live range of arena buffer `buf` that is current after op i have a reader other than the ops `but` (indices)
+    before the buffer's next writer?  An op that reads and rewrites the buffer is a reader first; NOPs and markers touch nothing."""
+    for j in range(i + 1, len(P.ops)):
+        r, w = op_tensors(P, j)
+        if buf in r and j not in but:
+            return True
+        if buf in w:
+            return False
+    return False
+
+
+def absorb(P, i, j):
+    """Op i runs inside op j from now on: it turns into ROMP_OP_NOP (fields intact: the fused kernel takes its weights from there)
+    and its flops move over; the caller sets bytes[j]."""
+    P.ops[i].kind = OP_NOP
+    P.flops[j] += P.flops[i]
+    P.flops[i] = P.bytes[i] = 0.0
+
+
+def attach_wave16(P, op, *shape):
+    """Give `op` the per-wave repack (pack_h2_wave16) of its f16x2 weights, seen as `shape`, in weight_aux (replaces the bf16x3 pack
+    of conv_math='all': a fused op runs no bf16x3 kernel) and ROMP_OPF_WAVE16, the launchers' dispatch flag (never weight_aux != NULL alone)."""
+    t = P.keep(pack_h2_wave16(P.by_ptr[op.weight_h2].view(*shape)))
+    op.weight_aux = t.data_ptr()
+    op.flags |= OPF_WAVE16
+
+
 def assign_formats(P):
     """Decide per activation tensor whether it lives in HBM as float32 or already split (H2), and write the choice into the
     ops.  A tensor (one live range of an arena buffer) is H2 iff conv_math offers the f16x2 kernels, every producer can write
@@ -180,15 +239,15 @@ def assign_formats(P):
     touched by anything else (max-pool, BEV head pieces, Conv1d, the host through romp_net_buffer_ptr) stay float32."""
     P.buf_fmt = {}                                           # buffer -> format of its LAST live range (for read_buffer)
     P.range_fallback = []                                    # (op index, name, max|x|): ops taken off the f16x2 kernels
-    if not getattr(P, 'f16x2', False):
+    if not P.f16x2:
         return
     gens, cur = [], {}
-    maxabs = getattr(P, 'op_maxabs', None)                   # per op: max|x| of its output (RompNet.calibrate), or None
+    maxabs = P.op_maxabs                                     # per op: max|x| of its output (RompNet.calibrate), or None
 
     def gen_for_write(buf):
         g = cur.get(buf)
         if g is None or gens[g]['read']:
-            gens.append(dict(buf=buf, ok=buf not in getattr(P, 'exported_bufs', ()), read=False, uses=[]))
+            gens.append(dict(buf=buf, ok=buf not in P.exported_bufs, read=False, uses=[]))
             cur[buf] = g = len(gens) - 1
         return gens[g]
 
@@ -245,22 +304,19 @@ def assign_formats(P):
             g = gen_for_write(op.out_buf)
             g['uses'].append((i, 'out'))
             g['ok'] &= oct_ok(op.out_cstride, op.out_coff)
-        elif op.kind in (OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT):
-            continue
-        else:                                                # any other op: its tensors stay float32
-            for b in (op.in_buf, op.res_buf):
-                if b >= 0:
-                    gen_for_read(b)['ok'] = False
-            for b in [op.out_buf] + ([op.term_buf[0]] if op.kind == OP_BEV_MAPS else []):     # BEV_MAPS has a second output
-                if b >= 0:
-                    gen_for_write(b)['ok'] = False
+        else:                                                # any other op: its tensors stay float32 (markers have none)
+            r, w = op_tensors(P, i)
+            for b in r:
+                gen_for_read(b)['ok'] = False
+            for b in w:
+                gen_for_write(b)['ok'] = False
     for g in gens:
         if maxabs is not None:                               # range safety: measured max|x| of the tensor's producers
             ms = [maxabs[i] for i, r in g['uses'] if r == 'out' and maxabs[i] is not None]
             if not any(r == 'out' for _, r in g['uses']):    # initialised from outside the program: the host may state its range
-                ms = [v for v in [getattr(P, 'buf_maxabs', {}).get(g['buf'])] if v is not None]
+                ms = [v for v in [P.buf_maxabs.get(g['buf'])] if v is not None]
             m = max(ms) if ms else None
-            if not h2_range_ok(m, getattr(P, 'calib_margin', CALIB_MARGIN)):
+            if not h2_range_ok(m, P.calib_margin):
                 g['ok'] = False
                 for i, r in g['uses']:
                     if r == 'in' and P.ops[i].kind == OP_CONV and P.ops[i].weight_h2:
@@ -268,10 +324,9 @@ def assign_formats(P):
                         P.ops[i].weight_h2, P.ops[i].scale_h2 = 0, 0
                         P.range_fallback.append((i, P.names[i] if i < len(P.names) else 'op%d' % i, m))
                         o = P.ops[i]
-                        if getattr(P, 'split_k_items', 0) and o.groups == 1 and o.Cin % 64 == 0 and o.Cout % 32 == 0 and o.ksize in (1, 3):
+                        if P.split_k_items and o.groups == 1 and o.Cin % 64 == 0 and o.Cout % 32 == 0 and o.ksize in (1, 3):
                             # split_k_groups left this layer whole for conv_h2k, which only runs on H2 tensors: on the f32 kernels it
                             # is a handful of work items with a serial loop over all input channels (slow at B = 1, still correct)
-                            import warnings
                             warnings.warn('single-image plan: %s fell back to the float32 kernels (max|x| %.3g outside the fp16 pieces) and '
                                           'runs WITHOUT its input-channel split -- expect a slower frame; calibrate on representative '
                                           'frames or lower with ROMP_KSPLIT_WG=0' % (P.names[i] if i < len(P.names) else 'op%d' % i, m))
@@ -315,11 +370,8 @@ def fuse_bottleneck_seams(P):
     256-channel output is never written or read (2 x 537 MB and one launch less at B = 32).  Only when nothing else reads that
     output and x0's buffer is still intact when the seam runs (build_hrnet32_backbone frees it one conv late for this);
     env ROMP_SEAM_DS=0 keeps the downsample a launch of its own (A/B runs)."""
-    import os
-    P.fused_seams = 0
-    if not getattr(P, 'f16x2', False) or os.environ.get('ROMP_FUSE_SEAMS', '1') not in ('1', 'all') or (getattr(P, 'split_k_items', 0) and os.environ.get('ROMP_FUSE_SEAMS', '1') != 'all'):
+    if not P.f16x2 or os.environ.get('ROMP_FUSE_SEAMS', '1') not in ('1', 'all') or (P.split_k_items and os.environ.get('ROMP_FUSE_SEAMS', '1') != 'all'):
         return 0
-    by_ptr = {c.data_ptr(): c for c in P.consts if isinstance(c, torch.Tensor)}
     for i in range(len(P.ops) - 1):
         a, b = P.ops[i], P.ops[i + 1]
         if not (a.kind == OP_CONV and b.kind == OP_CONV):
@@ -335,16 +387,11 @@ def fuse_bottleneck_seams(P):
               a.act_shift == b.act_shift)
         if not ok:
             continue
-        for o, shape in ((a, (1, 4, 2, 2, 256, 8)), (b, (1, 16, 2, 2, 64, 8))):
-            t = pack_h2_wave16(by_ptr[o.weight_h2].view(*shape))
-            P.consts.append(t)
-            o.weight_aux = t.data_ptr()
-            o.flags |= OPF_WAVE16
-        a.kind, b.kind = OP_NOP, OP_SEAM1X1
-        P.flops[i + 1] += P.flops[i]
-        P.flops[i] = 0.0
+        attach_wave16(P, a, 1, 4, 2, 2, 256, 8)
+        attach_wave16(P, b, 1, 16, 2, 2, 64, 8)
+        absorb(P, i, i + 1)
+        b.kind = OP_SEAM1X1
         P.bytes[i + 1] = 4.0 * a.H * a.W * (64 + 256 + 256 + 64)
-        P.bytes[i] = 0.0
         P.fused_seams += 1
         d = P.ops[i - 1] if i >= 1 else None
         if d is None or os.environ.get('ROMP_SEAM_DS', '1') == '0':
@@ -355,25 +402,13 @@ def fuse_bottleneck_seams(P):
                 d.stream == a.stream and (d.H, d.W) == (a.H, a.W) and d.in_fmt == FMT_H2 and d.out_fmt == FMT_H2 and
                 d.act_shift == a.act_shift and d.in_cstride % 8 == 0 and d.in_coff % 8 == 0 and
                 d.in_buf >= 0 and d.in_buf not in (a.out_buf, b.out_buf))           # x0 must still be there when the seam runs
-        for j in range(i + 1, len(P.ops)):                       # nobody else reads the downsample's output (until the buffer's next writer)
-            o = P.ops[j]
-            if not fold or (o.out_buf == d.out_buf and o.kind not in (OP_NOP, OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT)):
-                break
-            if d.out_buf in [o.in_buf, o.res_buf] + [o.term_buf[k] for k in range(o.n_terms)]:
-                fold = False
-        if not fold:
+        if not fold or read_elsewhere(P, i - 1, d.out_buf, but=(i + 1,)):   # nobody but the seam (as its residual) reads the downsample's output
             continue
-        t = pack_h2_wave16(by_ptr[d.weight_h2].view(1, 4, 2, 2, 256, 8))
-        P.consts.append(t)
-        d.weight_aux = t.data_ptr()
-        d.flags |= OPF_WAVE16
-        d.kind = OP_NOP
+        attach_wave16(P, d, 1, 4, 2, 2, 256, 8)
+        absorb(P, i - 1, i + 1)
         b.flags |= OPF_SEAM_DS
-        P.flops[i + 1] += P.flops[i - 1]
-        P.flops[i - 1] = 0.0
         P.bytes[i + 1] = 4.0 * a.H * a.W * (64 + 64 + 256 + 64)
-        P.bytes[i - 1] = 0.0
-        P.folded_downsamples = getattr(P, 'folded_downsamples', 0) + 1
+        P.folded_downsamples += 1
     return P.fused_seams
 
 
@@ -391,13 +426,10 @@ def fuse_up_sums(P):
     this kernel, on the launch-bound chain that costs more than the small convs did (frame 2.10 -> 2.54 ms in a same-box A/B).
     Measured at B = 32 (same box): serial kernel sum 12.02 -> 11.83 ms, images/s 2 996 -> 3 001: the up-convs used to hide on side
     streams.  Env ROMP_FUSEUP=0: off, =all: single-image plans too.  -> number of fused outputs."""
-    import os
-    P.fused_ups = 0
     mode = os.environ.get('ROMP_FUSEUP', '1')
-    if not getattr(P, 'f16x2', False) or mode == '0' or (getattr(P, 'split_k_items', 0) and mode != 'all'):
+    if not P.f16x2 or mode == '0' or (P.split_k_items and mode != 'all'):
         return 0
-    by_ptr = {c.data_ptr(): c for c in P.consts if isinstance(c, torch.Tensor)}
-    consumed = {}                                             # conv op index -> [fusesum op indices that took a slice of it]
+    consumed = set()                                          # the conv ops a sum took a slice of
     for fi, F in enumerate(P.ops):
         if F.kind != OP_FUSESUM or F.out_fmt != FMT_H2 or F.Cout not in FUP_TILE or F.n_terms < 2:
             continue
@@ -430,46 +462,33 @@ def fuse_up_sums(P):
             continue
         packs, scs, shs = [], [], []
         for j, U, c0 in prods:
-            w = by_ptr[U.weight_h2].view(1, U.Cin // 16, 2, 2, U.cout_pad, 8)[:, :, :, :, c0:c0 + F.Cout, :]
+            w = P.by_ptr[U.weight_h2].view(1, U.Cin // 16, 2, 2, U.cout_pad, 8)[:, :, :, :, c0:c0 + F.Cout, :]
             packs.append(pack_h2_wave16(w.contiguous()).reshape(-1))
-            scs.append(by_ptr[U.scale_h2].reshape(-1)[c0:c0 + F.Cout])
-            shs.append(by_ptr[U.shift].reshape(-1)[c0:c0 + F.Cout])
-        pw, ps, pb = torch.cat(packs).contiguous(), torch.stack(scs).contiguous(), torch.stack(shs).contiguous()
-        P.consts += [pw, ps, pb]
+            scs.append(P.by_ptr[U.scale_h2].reshape(-1)[c0:c0 + F.Cout])
+            shs.append(P.by_ptr[U.shift].reshape(-1)[c0:c0 + F.Cout])
+        pw, ps, pb = P.keep(torch.cat(packs).contiguous()), P.keep(torch.stack(scs).contiguous()), P.keep(torch.stack(shs).contiguous())
         F.kind = OP_FUSEUP
         F.weight_aux, F.scale_h2, F.shift = pw.data_ptr(), ps.data_ptr(), pb.data_ptr()
         F.flags |= OPF_WAVE16
-        up_bytes = 0.0
         for (j, U, c0), k in zip(prods, range(n_dir, F.n_terms)):
             # the term is now the conv's SOURCE; account the conv's share of flops / bytes to this op
             P.bytes[fi] += 4.0 * U.H * U.W * (U.Cin - F.Cout)          # reads x_s instead of the small term
             P.flops[fi] += 2.0 * U.H * U.W * U.Cin * F.Cout
             F.term_buf[k], F.term_cstride[k], F.term_coff[k] = U.in_buf, U.in_cstride, 0
-            consumed.setdefault(j, []).append(fi)
+            consumed.add(j)
         P.fused_ups += 1
-    # a conv whose every reader was fused no longer runs
-    for j, fis in consumed.items():
-        U = P.ops[j]
-        readers = [i for i in range(j + 1, len(P.ops))
-                   if any(P.ops[i].kind in (OP_FUSESUM,) and P.ops[i].term_buf[k] == U.out_buf for k in range(P.ops[i].n_terms))
-                   or (P.ops[i].kind in (OP_CONV, OP_KSUM) and (P.ops[i].in_buf == U.out_buf or P.ops[i].res_buf == U.out_buf))]
-        # (readers of a LATER live range of the same arena buffer come after its next writer: stop there)
-        nxt = [i for i in range(j + 1, len(P.ops)) if P.ops[i].out_buf == U.out_buf and P.ops[i].kind not in (OP_NOP, OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT)]
-        if nxt:
-            readers = [i for i in readers if i <= nxt[0]]
-        if not readers:
-            share = P.flops[j]
-            U.kind = OP_NOP
-            P.flops[j] = 0.0
-            P.bytes[j] = 0.0
+    for j in sorted(consumed):                                # a conv whose every reader was fused no longer runs (its flops went to the sums above)
+        if not read_elsewhere(P, j, P.ops[j].out_buf):
+            P.ops[j].kind = OP_NOP
+            P.flops[j] = P.bytes[j] = 0.0
     return P.fused_ups
 
 
 def stream_races(P):
     """Happens-before check of a lowered program: stream order + FORK / JOIN + RECORD / WAIT must order every pair of conflicting
     accesses to an arena buffer (write -> read, read -> write, write -> write; whole buffers, channel slices ignored: conservative
-    for merged convs, whose slices share their writer anyway).  -> list of (kind, buffer, earlier op, later op).  Program.op_array()
-    refuses a program with races; tests/test_cpu_host.py runs it on every plan kind."""
+    for merged convs, whose slices share their writer anyway; what an op touches: op_tensors).  -> list of (kind, buffer, earlier op,
+    later op).  Program.op_array() refuses a program with races; tests/test_cpu_host.py runs it on every plan kind."""
     NS = 4
     ops = P.ops
     vc = [[-1] * NS for _ in range(NS)]                      # vc[s][t]: the latest op of stream t that happens-before stream s's next op
@@ -493,22 +512,6 @@ def stream_races(P):
             vc[s][s] = i
             at[i] = (s, list(vc[s]))
 
-    def touched(i):
-        op, r, w = ops[i], [], []
-        srcs = [op] + ([ops[i - 1]] if op.kind in (OP_BBLOCK32, OP_BBLOCK64, OP_SEAM1X1) else [])    # a fused pair: the NOP before it holds the first conv
-        seam_ds = op.kind == OP_SEAM1X1 and (op.flags & OPF_SEAM_DS)
-        if seam_ds:                                              # the folded downsample: its input is read, its output never materialises
-            r.append(ops[i - 2].in_buf)
-        for o in srcs:
-            if o.kind == OP_STEM2:                               # reads the caller's image only (its in_buf names the tensor that no longer exists)
-                w += [o.out_buf] if o.out_buf >= 0 else []
-                continue
-            r += [b for b in ((o.in_buf,) if (seam_ds and o is not op) else (o.in_buf, o.res_buf)) if b >= 0]
-            if o.kind in (OP_FUSESUM, OP_FUSEUP):
-                r += [o.term_buf[k] for k in range(o.n_terms) if o.term_buf[k] >= 0]
-            w += [b for b in [o.out_buf] + ([o.term_buf[0]] if o.kind == OP_BEV_MAPS else []) if b >= 0]
-        return r, w
-
     ordered = lambda i, j: at[j][1][at[i][0]] >= i           # op i happens-before op j (i earlier in op order)
 
     def interleaved(i, j):
@@ -526,7 +529,7 @@ def stream_races(P):
     for j in range(len(ops)):
         if at[j] is None:
             continue
-        r, w = touched(j)
+        r, w = op_tensors(P, j)
         for b in r:
             i = last_w.get(b)
             if i is not None and not ordered(i, j):
@@ -551,18 +554,11 @@ def fuse_basic_blocks(P):
     (64 tiles there, a quarter of the CUs, but 32 fewer launches on a launch-bound chain: network 2.15 -> 1.95 ms at B = 1; the
     64-channel kernel would run 32 tiles: 2.25 -> 2.45 ms per frame).  Env ROMP_FUSE_BLOCKS: 0 off, 32 / 64 one class, all
     both everywhere (A/B runs).  -> number of fused blocks."""
-    import os
-    P.fused_blocks = 0
-    if not getattr(P, 'f16x2', False) or os.environ.get('ROMP_FUSE_BLOCKS', '1') == '0':
+    if not P.f16x2 or os.environ.get('ROMP_FUSE_BLOCKS', '1') == '0':
         return 0
     fuse_c = {'1': (32, 64), '32': (32,), '64': (64,), 'all': (32, 64)}.get(os.environ.get('ROMP_FUSE_BLOCKS', '1'), (32, 64))
-    if getattr(P, 'split_k_items', 0) and os.environ.get('ROMP_FUSE_BLOCKS', '1') == '1':
+    if P.split_k_items and os.environ.get('ROMP_FUSE_BLOCKS', '1') == '1':
         fuse_c = (32,)                                         # a single image is 32 tiles of the 64-channel kernel: slower than its two convs
-    readers = {}
-    for i, op in enumerate(P.ops):
-        for b in [op.in_buf, op.res_buf] + [op.term_buf[k] for k in range(op.n_terms if op.kind == OP_FUSESUM else 0)]:
-            if b >= 0:
-                readers.setdefault(b, []).append(i)
     for i in range(len(P.ops) - 1):
         a, b = P.ops[i], P.ops[i + 1]
         if not (a.kind == OP_CONV and b.kind == OP_CONV):
@@ -575,50 +571,30 @@ def fuse_basic_blocks(P):
                    (b.res_cstride, b.res_coff) == (a.in_cstride, a.in_coff) and (b.in_cstride, b.in_coff) == (a.out_cstride, a.out_coff) and
                    a.stream == b.stream and (a.H, a.W) == (b.H, b.W))
         h2 = a.in_fmt == FMT_H2 and a.out_fmt == FMT_H2 and b.in_fmt == FMT_H2 and b.res_fmt == FMT_H2 and b.out_fmt == FMT_H2
-        # the intermediate tensor must die in the second conv: nobody else reads that live range of its buffer
-        later = [j for j in readers.get(a.out_buf, []) if j > i + 1]
-        writers_between = [j for j in range(i + 2, later[0] + 1) if P.ops[j].out_buf == a.out_buf] if later else [0]
-        private = not later or bool(writers_between)
-        if plain and chained and h2 and private and a.act_shift == b.act_shift:
+        # (last: the intermediate tensor must die in the second conv -- nobody else reads that live range of its buffer)
+        if plain and chained and h2 and a.act_shift == b.act_shift and not read_elsewhere(P, i, a.out_buf, but=(i + 1,)):
             # the row-pipelined kernels (conv_h2c.h) read their weights per wave (16 output channels each).  32 channels: batch plans only
             # (two workgroups per CU; a single image's tiles are better off on conv_h2b.hip's kernel: 2.10 vs 2.15 ms at B = 1)
             # (round 4 A/B runs, both neutral: conv_h2b's kernel in batch plans, the row-pipelined one at B = 1 -- 1.436 / 1.479 vs 1.458 / 1.461 ms)
-            if C_ == 64 or not getattr(P, 'split_k_items', 0):
-                by_ptr = {c.data_ptr(): c for c in P.consts if isinstance(c, torch.Tensor)}
+            if C_ == 64 or not P.split_k_items:
                 for o in (a, b):
-                    t = pack_h2_wave16(by_ptr[o.weight_h2].view(9, C_ // 16, 2, 2, C_, 8))
-                    P.consts.append(t)
-                    o.weight_aux = t.data_ptr()          # (replaces the bf16x3 pack of conv_math='all': a fused op runs no bf16x3 kernel)
-                    o.flags |= OPF_WAVE16                # the dispatch flag of launch_bblock32 / 64: never weight_aux != NULL alone
-            a.kind, b.kind = OP_NOP, (OP_BBLOCK32 if C_ == 32 else OP_BBLOCK64)
-            P.flops[i + 1] += P.flops[i]
-            P.flops[i] = 0.0
+                    attach_wave16(P, o, 9, C_ // 16, 2, 2, C_, 8)
+            absorb(P, i, i + 1)
+            b.kind = OP_BBLOCK32 if C_ == 32 else OP_BBLOCK64
             P.bytes[i + 1] = 4.0 * a.H * a.W * C_ * 2
-            P.bytes[i] = 0.0
             P.fused_blocks += 1
     return P.fused_blocks
 
 
 def _stem7p_pair(P, i):
     """ops[i - 1], ops[i] = ResNet-50's stem conv (MFMA-eligible) and the max-pool that is the only reader of its output?"""
-    import os
-    if not getattr(P, 'f16x2', False) or os.environ.get('ROMP_FUSE_STEM7P', '1') == '0' or i != 1:
+    if not P.f16x2 or os.environ.get('ROMP_FUSE_STEM7P', '1') == '0' or i != 1:
         return False
     a, b = P.ops[0], P.ops[1]
-    if not (a.kind == OP_STEM7 and b.kind == OP_MAXPOOL and not (a.flags & OPF_STEM_VALU) and a.out_buf >= 0 and b.in_buf == a.out_buf and
+    return (a.kind == OP_STEM7 and b.kind == OP_MAXPOOL and not (a.flags & OPF_STEM_VALU) and a.out_buf >= 0 and b.in_buf == a.out_buf and
             b.in_cstride == a.out_cstride and a.out_coff == 0 and a.Cout == 64 and b.Cin == 64 and a.H % 32 == 0 and a.W % 32 == 0 and
-            (b.H, b.W) == (a.H // 2, a.W // 2) and a.stream == b.stream and b.out_buf >= 0 and (b.out_cstride & 3) == 0):
-        return False
-    for j in range(2, len(P.ops)):                               # the conv's output must die in the pool
-        o = P.ops[j]
-        if o.kind in (OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT):
-            continue
-        reads = [o.in_buf, o.res_buf] + [o.term_buf[k] for k in range(o.n_terms if o.kind in (OP_FUSESUM, OP_FUSEUP) else 0)]
-        if a.out_buf in reads:
-            return False
-        if o.out_buf == a.out_buf and o.kind != OP_NOP:
-            break
-    return True
+            (b.H, b.W) == (a.H // 2, a.W // 2) and a.stream == b.stream and b.out_buf >= 0 and (b.out_cstride & 3) == 0 and
+            not read_elsewhere(P, 0, a.out_buf, but=(1,)))               # the conv's output must die in the pool
 
 
 def fuse_stem7p(P):
@@ -628,18 +604,15 @@ def fuse_stem7p(P):
     pass decided).  The 64-channel half-resolution tensor (16.8 MB per image) is never written or read.  f16x2 programs only (the
     float32 / calibration programs keep the exact VALU conv), weights within the fp16 pieces (ROMP_OPF_STEM_VALU otherwise, set by
     resnet_plan._stem7; env ROMP_STEM=valu forces it), env ROMP_FUSE_STEM7P=0: off (A/B runs).  -> 1 if fused."""
-    P.fused_stem7p = 0
     if len(P.ops) < 2 or not _stem7p_pair(P, 1):
         return 0
     a, b = P.ops[0], P.ops[1]
     b.weight, b.scale, b.shift = a.weight, a.scale, a.shift
     b.H, b.W, b.Cin, b.Cout, b.ksize, b.stride, b.relu, b.groups = a.H, a.W, 3, 64, 7, 2, 1, 1
     b.in_buf, b.in_cstride, b.in_coff = BUF_IMAGE, 3, 0
-    a.kind, b.kind = OP_NOP, OP_STEM7P
-    P.flops[1] += P.flops[0]
-    P.flops[0] = 0.0
+    absorb(P, 0, 1)
+    b.kind = OP_STEM7P
     P.bytes[1] = 4.0 * (a.H * a.W * 3 + (a.H // 4) * (a.W // 4) * 64)        # the image in, the pooled tensor out
-    P.bytes[0] = 0.0
     P.fused_stem7p = 1
     return 1
 
@@ -650,9 +623,7 @@ def fuse_stem2(P):
     stem's op turns into ROMP_OP_NOP (fields intact: the kernel takes weights / BN from there), the conv into ROMP_OP_STEM2 with
     its weights repacked per wave (pack_h2_wave16).  The 64-channel half-resolution tensor is never written or read: 2 x 16.8 MB
     per image off the serial head of the graph.  Env ROMP_FUSE_STEM2=0: off (A/B runs).  -> 1 if fused."""
-    import os
-    P.fused_stem2 = 0
-    if not getattr(P, 'f16x2', False) or os.environ.get('ROMP_FUSE_STEM2', '1') == '0' or len(P.ops) < 2:
+    if not P.f16x2 or os.environ.get('ROMP_FUSE_STEM2', '1') == '0' or len(P.ops) < 2:
         return 0
     a, b = P.ops[0], P.ops[1]
     if not (a.kind == OP_STEM and b.kind == OP_CONV):
@@ -663,27 +634,12 @@ def fuse_stem2(P):
           b.res_buf < 0 and b.weight_h2 and b.scale_h2 and b.in_fmt == FMT_H2 and b.out_fmt == FMT_H2 and b.pad_h == -1 and b.pad_w == -1 and
           b.out_rstride == 0 and b.out_bstride == 0 and b.out_buf >= 0 and (b.H, b.W) == (a.H // 2, a.W // 2) and a.stream == b.stream and
           a.act_shift == b.act_shift and ((b.out_cstride | b.out_coff) & 7) == 0)
-    if not ok:
+    if not ok or read_elsewhere(P, 0, a.out_buf, but=(1,)):      # the stem's output must die in that conv: nobody else reads this live range
         return 0
-    for j in range(2, len(P.ops)):                               # the stem's output must die in that conv: nobody else reads this live range
-        o = P.ops[j]
-        if o.kind in (OP_FORK, OP_JOIN, OP_RECORD, OP_WAIT):
-            continue
-        reads = [o.in_buf, o.res_buf] + [o.term_buf[k] for k in range(o.n_terms if o.kind in (OP_FUSESUM, OP_FUSEUP) else 0)]
-        if a.out_buf in reads:
-            return 0
-        if o.out_buf == a.out_buf and o.kind != OP_NOP:
-            break                                                  # (the buffer starts a new life)
-    by_ptr = {c.data_ptr(): c for c in P.consts if isinstance(c, torch.Tensor)}
-    t = pack_h2_wave16(by_ptr[b.weight_h2].view(9, 4, 2, 2, 64, 8))
-    P.consts.append(t)
-    b.weight_aux = t.data_ptr()
-    b.flags |= OPF_WAVE16
-    a.kind, b.kind = OP_NOP, OP_STEM2
-    P.flops[1] += P.flops[0]
-    P.flops[0] = 0.0
+    attach_wave16(P, b, 9, 4, 2, 2, 64, 8)
+    absorb(P, 0, 1)
+    b.kind = OP_STEM2
     P.bytes[1] = 4.0 * (a.H * a.W * 3 + (b.H // 2) * (b.W // 2) * 64)      # the image in, y out
-    P.bytes[0] = 0.0
     P.fused_stem2 = 1
     return 1
 
@@ -697,7 +653,8 @@ class Program:
         self.names: List[str] = []
         self.flops: List[float] = []          # per image
         self.bytes: List[float] = []          # algorithmic HBM bytes per image (in + out + res)
-        self.consts: List[torch.Tensor] = []
+        self.consts: List[torch.Tensor] = []                   # packed constants in export order; add them with keep()
+        self.by_ptr: Dict[int, object] = {}                    # address an op's pointer field holds -> that constant
         self.buf_floats: List[int] = []
         self._free: Dict[int, List[int]] = {}
         self._pfree: Dict[int, Dict[int, List[int]]] = {}     # per-stream free lists inside a fork/join region
@@ -716,6 +673,12 @@ class Program:
         self.head_in_buf: Optional[int] = None
         self.head_in_ch, self.coord_off = HEAD_IN_CH, None     # coord_off: first of the two constant CoordConv channels
         self.split_k_items = 0                                 # > 0 (single-image plans): split a conv's input channels until it has this many work items
+        self.op_maxabs: Optional[List] = None                  # per op: max|x| of its output (RompNet.calibrate), or None: not measured
+        self.buf_maxabs: Dict[int, float] = {}                 # the same for buffers initialised from outside the program
+        self.calib_margin = CALIB_MARGIN
+        self.range_fallback: List = []                         # (op index, name, max|x|): ops assign_formats took off the f16x2 kernels
+        self.fused_stem2 = self.fused_stem7p = self.fused_blocks = self.fused_seams = self.fused_ups = self.folded_downsamples = 0
+        self._lowered = False
 
     # ---- buffers -------------------------------------------------------------------------
     def alloc(self, floats, persistent=False):
@@ -777,10 +740,7 @@ class Program:
         op.kind, op.Cin = kind, n
         op.stream = self.cur_stream if kind in (OP_RECORD, OP_WAIT) else 0
         op.in_buf = op.out_buf = op.res_buf = BUF_NONE
-        self.ops.append(op)
-        self.names.append({OP_FORK: 'fork', OP_JOIN: 'join', OP_RECORD: 'record', OP_WAIT: 'wait'}[kind])
-        self.flops.append(0.0)
-        self.bytes.append(0.0)
+        self.emit(op, {OP_FORK: 'fork', OP_JOIN: 'join', OP_RECORD: 'record', OP_WAIT: 'wait'}[kind], 0.0, 0.0)
 
     def fork(self, n_side):
         """Side streams 1..n_side may run concurrently with the main stream until join()."""
@@ -806,10 +766,21 @@ class Program:
     def new_act(self, C_, H, W):
         return Act(self.alloc(C_ * H * W), C_, H, W, C_)
 
+    def keep(self, c):
+        """Keep a packed constant (a tensor, or a ctypes array passed by value from the host) alive and findable by its address."""
+        self.consts.append(c)
+        self.by_ptr[c.data_ptr() if isinstance(c, torch.Tensor) else C.addressof(c)] = c
+        return c
+
     def _dev(self, t):
-        t = t.to(self.device).contiguous()
-        self.consts.append(t)
-        return t
+        return self.keep(t.to(self.device).contiguous())
+
+    def emit(self, op, name, flops, nbytes):
+        """Append one op with its name, its flops and its algorithmic HBM bytes (both per image)."""
+        self.ops.append(op)
+        self.names.append(name)
+        self.flops.append(flops)
+        self.bytes.append(nbytes)
 
     # ---- ops -----------------------------------------------------------------------------
     def split_k_groups(self, cin, cout, ksize, stride, Ho, Wo):
@@ -818,7 +789,6 @@ class Program:
         ksum_kernel adds the partial sums)."""
         if self.split_k_items <= 0 or ksize not in (1, 3) or Wo % 16 or cout % 8:
             return 1
-        import os
         if self.f16x2 and (stride == 1 or ksize == 3) and cin % 64 == 0 and cout % 32 == 0 and os.environ.get('ROMP_KSPLIT_WG', '1') != '0':
             # round 4: csrc/conv_h2k.hip splits the input channels across the WAVES of a workgroup and reduces in LDS -- the layer
             # stays one conv op (no float32 partial tensors, no ksum launch); the autotuner picks it wherever the tensors are H2
@@ -862,10 +832,7 @@ class Program:
         op.scale, op.shift = ps.data_ptr(), pb.data_ptr()
         op.relu_from = relu_from
         op.stream = self.cur_stream
-        self.ops.append(op)
-        self.names.append(name + '.ksum')
-        self.flops.append(float(part.H * part.W * cout * (G + 1)))
-        self.bytes.append(4.0 * part.H * part.W * cout * (G + 1 + (1 if res is not None else 0)))
+        self.emit(op, name + '.ksum', float(part.H * part.W * cout * (G + 1)), 4.0 * part.H * part.W * cout * (G + 1 + (1 if res is not None else 0)))
         self.free(part)
         return out
 
@@ -922,11 +889,8 @@ class Program:
             psh = self._dev(psh.float())
             op.weight_h2, op.scale_h2, op.act_shift = ph.data_ptr(), psh.data_ptr(), ACT_SHIFT
         op.stream = self.cur_stream
-        self.ops.append(op)
-        self.names.append(name)
-        self.flops.append(2.0 * Ho * Wo * cout * cin * kh * kw * groups)
-        nbytes = 4.0 * (x.H * x.W * cin_phys * groups + Ho * Wo * cout * groups * (2 if res is not None else 1))
-        self.bytes.append(nbytes)
+        self.emit(op, name, 2.0 * Ho * Wo * cout * cin * kh * kw * groups,
+                  4.0 * (x.H * x.W * cin_phys * groups + Ho * Wo * cout * groups * (2 if res is not None else 1)))
         return out
 
     def stem(self, name, w, scale, shift, H, W):
@@ -940,14 +904,10 @@ class Program:
         op.weight, op.scale, op.shift = pw.data_ptr(), ps.data_ptr(), pb.data_ptr()
         # stem_mfma_kernel splits 256 w into fp16 pieces: a weight beyond +-255.9 would be clamped -> the exact float32
         # VALU kernel for such a checkpoint; env ROMP_STEM=valu forces it (A/B runs)
-        import os
         wmax = float(w.abs().max()) if w.numel() else 0.0
         if os.environ.get('ROMP_STEM', '') == 'valu' or not (wmax * 256.0 < 65504.0):
             op.flags |= OPF_STEM_VALU
-        self.ops.append(op)
-        self.names.append(name)
-        self.flops.append(2.0 * (H // 2) * (W // 2) * 64 * 27)
-        self.bytes.append(4.0 * (H * W * 3 + (H // 2) * (W // 2) * 64))
+        self.emit(op, name, 2.0 * (H // 2) * (W // 2) * 64 * 27, 4.0 * (H * W * 3 + (H // 2) * (W // 2) * 64))
         return out
 
     def fusesum(self, name, terms: List[Act], shifts: List[int], relu=True, out: Optional[Act] = None):
@@ -966,19 +926,16 @@ class Program:
             op.term_buf[k], op.term_shift[k], op.term_cstride[k], op.term_coff[k] = t.buf, s, t.cstride, t.coff
             nbytes += 4.0 * t.H * t.W * t.C
         op.stream = self.cur_stream
-        self.ops.append(op)
-        self.names.append(name)
-        self.flops.append(float(H * W * t0.C * (len(terms) - 1)))
-        self.bytes.append(nbytes)
+        self.emit(op, name, float(H * W * t0.C * (len(terms) - 1)), nbytes)
         return out
 
     def op_array(self):
         """The lowered op list as a ctypes array.  Lowering (tensor formats, block fusion) happens on the first call; later calls
         (export.save_plan on a program its net already created) return the same ops -- the format pass reads conv kinds and
         must not see the fused ones."""
-        if not getattr(self, '_lowered', False):
+        if not self._lowered:
             assign_formats(self)
-            fuse_stem2(self)                 # (first: its reader analysis wants every op still a plain conv)
+            fuse_stem2(self)
             fuse_stem7p(self)
             fuse_basic_blocks(self)
             fuse_bottleneck_seams(self)
@@ -1034,7 +991,6 @@ def build_hrnet32_backbone(P: Program, sd, input_size=512, out_cstride=32) -> Ac
     # ---- transition1 (model.py:393-398)
     # (the two transition convs read the same tensor and are independent: two streams -- scripts/timeline.py counts 3.9 ms of a
     # forward with a single kernel in flight; every pair that can co-run takes some of it back)
-    import os
     merge_s2 = os.environ.get('ROMP_MERGE_S2', '1') != '0'       # A/B switch: 0 = one launch per stride-2 conv as in rounds 1-3
     # Round 4: the stages form ONE open fork .. join region with point-to-point edges (ROMP_OP_RECORD / ROMP_OP_WAIT) instead of two
     # full fork/join barriers per module: branch j lives on stream j from transition1 to the last module; a fuse output waits for

@@ -11,6 +11,8 @@ romp/lib/models/basic_modules.py Bottleneck :90-128, romp/lib/models/romp_model.
              transposed conv's FLOPs, no zero-stuffing, no col2im pass
   * head     the three towers of plan.build_romp_head on [64 features | 2 CoordConv | 6 pad] channels
 """
+import os
+
 import torch
 
 from .lib import RompOp, OPF_STEM_VALU
@@ -32,13 +34,10 @@ def _stem7(P: Program, name, w, scale, shift, H, W):
     op.weight, op.scale, op.shift = pw.data_ptr(), ps.data_ptr(), pb.data_ptr()
     # the MFMA form (plan.fuse_stem7p: conv + pool as one kernel) splits 256 w into fp16 pieces: a weight beyond +-255.9 would be clamped
     # -> the exact float32 VALU kernel + the pool for such a checkpoint; env ROMP_STEM=valu forces it (A/B runs, tests)
-    import os
     wmax = float(w.abs().max()) if w.numel() else 0.0
     if os.environ.get('ROMP_STEM', '') == 'valu' or not (wmax * 256.0 < 65504.0):
         op.flags |= OPF_STEM_VALU
-    P.ops.append(op); P.names.append(name)
-    P.flops.append(2.0 * (H // 2) * (W // 2) * 64 * 147)
-    P.bytes.append(4.0 * (H * W * 3 + (H // 2) * (W // 2) * 64))
+    P.emit(op, name, 2.0 * (H // 2) * (W // 2) * 64 * 147, 4.0 * (H * W * 3 + (H // 2) * (W // 2) * 64))
     return out
 
 
@@ -48,9 +47,7 @@ def _maxpool(P: Program, name, x: Act):
     op.kind, op.in_buf, op.out_buf, op.res_buf = OP_MAXPOOL, x.buf, out.buf, BUF_NONE
     op.H, op.W, op.Cin, op.Cout, op.ksize, op.stride = x.H, x.W, x.C, x.C, 3, 2
     op.in_cstride, op.out_cstride = x.cstride, out.cstride
-    P.ops.append(op); P.names.append(name)
-    P.flops.append(9.0 * out.H * out.W * x.C)
-    P.bytes.append(4.0 * (x.H * x.W * x.C + out.H * out.W * x.C))
+    P.emit(op, name, 9.0 * out.H * out.W * x.C, 4.0 * (x.H * x.W * x.C + out.H * out.W * x.C))
     return out
 
 

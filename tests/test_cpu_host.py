@@ -679,3 +679,188 @@ def test_downsample_fold_needs_an_intact_block_input(monkeypatch):
     P, a0, at, au = lower(False, True)
     assert P.fused_seams == 1 and getattr(P, 'folded_downsamples', 0) == 0 and P.ops[2].kind == L.OP_CONV
 
+
+
+def _wsb(co, ci, k=1):
+    """(weights, scale, shift) of one small conv layer, as Program.conv takes them."""
+    return [torch.full((co, ci, k, k), 0.01)], [torch.ones(co)], [torch.zeros(co)]
+
+
+def _seam_program():
+    """layer1's first seam in small: x0, conv1 `m`, the downsample `d`, conv3 `t` (+ d) and the next block's conv1 `u`."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, set_conv_math
+    P = Program('cpu')
+    set_conv_math(P, 'f16x2')
+    a0 = P.conv('x0', Act(L.BUF_IMAGE, 64, 16, 16, 64), *_wsb(64, 64), 1, 1, True)
+    am = P.conv('m', a0, *_wsb(64, 64), 1, 1, True)
+    ad = P.conv('d', a0, *_wsb(256, 64), 1, 1, False)
+    at = P.conv('t', am, *_wsb(256, 64), 1, 1, True, res=ad)
+    au = P.conv('u', at, *_wsb(64, 256), 1, 1, True)
+    P.op_array()
+    return P, a0, am, ad, at, au
+
+
+def _fuseup_program(block_on_up):
+    """A two-branch fuse output: x0 (32 ch), x1 (64 ch at half the resolution), the 1x1 up-conv of x1 and the sum; `block_on_up`: a
+    BasicBlock reads the up-conv's output as well."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, set_conv_math
+    P = Program('cpu')
+    set_conv_math(P, 'f16x2')
+    x0 = P.conv('x0', Act(L.BUF_IMAGE, 32, 64, 64, 32), *_wsb(32, 32, 3), 3, 1, True)
+    x1 = P.conv('x1', x0, *_wsb(64, 32, 3), 3, 2, True)
+    up = P.conv('up', x1, *_wsb(32, 64), 1, 1, False)
+    out = P.fusesum('fuse', [x0, up], [0, 1], True)
+    P.conv('sink', out, *_wsb(32, 32), 1, 1, False)          # an H2 consumer keeps `out` in the H2 format
+    if block_on_up:
+        t = P.conv('b.conv1', up, *_wsb(32, 32, 3), 3, 1, True)
+        P.conv('b.conv2', t, *_wsb(32, 32, 3), 3, 1, True, res=up)
+    P.op_array()
+    return P, x0, x1, up
+
+
+def test_op_tensors_of_every_kind_the_builders_emit():
+    """plan.op_tensors is the one enumeration of what a launch reads and writes (the format pass, the fusion passes' liveness query
+    and the race check all ask it): one op of every kind plan.py, bev_plan.py and resnet_plan.py emit, before lowering."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, op_tensors
+    from romp_amd.resnet_plan import OP_MAXPOOL, OP_STEM7, _maxpool, _stem7
+    P = Program('cpu')                                       # float32 single-image plan: a split-K layer is conv.splitk + ksum
+    P.split_k_items = 128
+    x = P.stem('stem', torch.zeros(64, 3, 3, 3), torch.ones(64), torch.zeros(64), 64, 64)
+    P.fork(1)
+    P.on(1)
+    y = P.conv('c', x, *_wsb(64, 64), 1, 1, True)
+    e = P.record()
+    P.on(0)
+    q = P.conv('q', x, *_wsb(4, 64), 1, 1, False)
+    r = P.conv('r', x, *_wsb(4, 64), 1, 1, True, res=q)
+    P.wait(e)
+    s = P.fusesum('sum', [q, r], [0, 0])
+    P.join()
+    m = _maxpool(P, 'pool', _stem7(P, 'stem7', torch.zeros(64, 3, 7, 7), torch.ones(64), torch.zeros(64), 64, 64))
+    for name, kind, bufs in (('pack', L.OP_BEV_PACK, (q.buf, r.buf, 90)), ('maps', L.OP_BEV_MAPS, (q.buf, 90, 91)),
+                             ('conv3d', L.OP_CONV3D, (91, 92, L.BUF_CENTER))):
+        op = L.RompOp()
+        op.kind, (op.in_buf, op.res_buf, op.out_buf) = kind, bufs
+        if kind == L.OP_BEV_MAPS:
+            op.term_buf[0] = 92                              # the second output
+        P.emit(op, name, 0.0, 0.0)
+    part = P.ops[P.names.index('c.splitk')].out_buf
+    t7 = P.ops[P.names.index('stem7')].out_buf
+    expect = {'stem': ([], [x.buf]), 'fork': ([], []), 'c.splitk': ([x.buf], [part]), 'c.ksum': ([part], [y.buf]), 'record': ([], []),
+              'q': ([x.buf], [q.buf]), 'r': ([x.buf, q.buf], [r.buf]), 'wait': ([], []), 'sum': ([q.buf, r.buf], [s.buf]), 'join': ([], []),
+              'stem7': ([], [t7]), 'pool': ([t7], [m.buf]), 'pack': ([q.buf, r.buf], [90]), 'maps': ([q.buf, 90], [91, 92]),
+              'conv3d': ([91, 92], [])}
+    assert P.names == list(expect)
+    assert {o.kind for o in P.ops} == {L.OP_STEM, L.OP_FORK, L.OP_CONV, L.OP_KSUM, L.OP_RECORD, L.OP_WAIT, L.OP_FUSESUM, L.OP_JOIN, OP_STEM7,
+                                       OP_MAXPOOL, L.OP_BEV_PACK, L.OP_BEV_MAPS, L.OP_CONV3D}
+    for i, name in enumerate(P.names):
+        assert op_tensors(P, i) == expect[name], name
+    P.ops[P.names.index('r')].kind = L.OP_NOP                # a NOP keeps its fields and touches nothing
+    assert op_tensors(P, P.names.index('r')) == ([], [])
+
+
+def test_op_tensors_of_the_fused_kinds(monkeypatch):
+    """plan.op_tensors after lowering: a fused pair also reads what the NOP before it (its first conv) read; the OPF_SEAM_DS seam
+    reads the folded downsample's INPUT and not its output; the fused stems read no arena buffer; FUSEUP reads the sources of the
+    1x1 convs it absorbed; the NOPs touch nothing."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, op_tensors, set_conv_math
+    from romp_amd.resnet_plan import _maxpool, _stem7
+    for v in ('ROMP_FUSE_BLOCKS', 'ROMP_FUSE_SEAMS', 'ROMP_SEAM_DS', 'ROMP_FUSEUP', 'ROMP_FUSE_STEM2', 'ROMP_FUSE_STEM7P', 'ROMP_STEM'):
+        monkeypatch.delenv(v, raising=False)
+    for Cc, kind in ((32, L.OP_BBLOCK32), (64, L.OP_BBLOCK64)):
+        P = Program('cpu')
+        set_conv_math(P, 'f16x2')
+        a0 = P.conv('c0', Act(L.BUF_IMAGE, Cc, 16, 16, Cc), *_wsb(Cc, Cc, 3), 3, 1, True)
+        a1 = P.conv('c1', a0, *_wsb(Cc, Cc, 3), 3, 1, True)
+        a2 = P.conv('c2', a1, *_wsb(Cc, Cc, 3), 3, 1, True, res=a0)
+        P.op_array()
+        assert [o.kind for o in P.ops] == [L.OP_CONV, L.OP_NOP, kind] and P.ops[1].in_buf == a0.buf
+        r, w = op_tensors(P, 2)
+        assert sorted(set(r)) == sorted([a0.buf, a1.buf]) and sorted(w) == sorted([a1.buf, a2.buf])
+        P.ops[2].res_buf = L.BUF_NONE                        # (the block input is read through the NOP, not only as the residual)
+        assert a0.buf in op_tensors(P, 2)[0] and op_tensors(P, 1) == ([], [])
+    P, a0, am, ad, at, au = _seam_program()
+    assert [o.kind for o in P.ops] == [L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_NOP, L.OP_SEAM1X1] and P.ops[4].flags & L.OPF_SEAM_DS
+    r, w = op_tensors(P, 4)
+    assert sorted(r) == sorted([a0.buf, am.buf, at.buf]) and ad.buf not in r and sorted(w) == sorted([at.buf, au.buf])
+    assert op_tensors(P, 2) == op_tensors(P, 3) == ([], [])
+    monkeypatch.setenv('ROMP_SEAM_DS', '0')
+    P, a0, am, ad, at, au = _seam_program()
+    assert [o.kind for o in P.ops] == [L.OP_CONV, L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_SEAM1X1] and not (P.ops[4].flags & L.OPF_SEAM_DS)
+    r, w = op_tensors(P, 4)
+    assert sorted(r) == sorted([am.buf, ad.buf, at.buf]) and a0.buf not in r and sorted(w) == sorted([at.buf, au.buf])
+    monkeypatch.delenv('ROMP_SEAM_DS')
+    P = Program('cpu')                                       # HRNet's stem: STEM + conv2
+    set_conv_math(P, 'f16x2')
+    x = P.stem('stem', torch.full((64, 3, 3, 3), 0.01), torch.ones(64), torch.zeros(64), 64, 64)
+    y = P.conv('conv2', x, *_wsb(64, 64, 3), 3, 2, True)
+    P.conv('sink', y, *_wsb(32, 64), 1, 1, False)
+    P.op_array()
+    assert [o.kind for o in P.ops[:2]] == [L.OP_NOP, L.OP_STEM2] and P.ops[1].in_buf == x.buf
+    assert op_tensors(P, 0) == ([], []) and op_tensors(P, 1) == ([], [y.buf])
+    P = Program('cpu')                                       # ResNet-50's stem: STEM7 + MAXPOOL
+    set_conv_math(P, 'f16x2')
+    y = _maxpool(P, 'pool', _stem7(P, 'stem', torch.full((64, 3, 7, 7), 0.01), torch.ones(64), torch.zeros(64), 64, 64))
+    P.op_array()
+    assert [o.kind for o in P.ops] == [L.OP_NOP, L.OP_STEM7P]
+    assert op_tensors(P, 0) == ([], []) and op_tensors(P, 1) == ([], [y.buf])
+    P, x0, x1, up = _fuseup_program(False)
+    kinds = [o.kind for o in P.ops]
+    assert kinds == [L.OP_CONV, L.OP_CONV, L.OP_NOP, L.OP_FUSEUP, L.OP_CONV], kinds
+    r, w = op_tensors(P, 3)
+    assert r == [x0.buf, x1.buf] and up.buf not in r and w == [P.ops[3].out_buf]
+
+
+def test_read_elsewhere_follows_one_live_range():
+    """plan.read_elsewhere, the fusion passes' liveness query: readers count up to the buffer's next writer, an op that reads and
+    rewrites the buffer is a reader first, NOPs and markers neither read nor write whatever their fields say."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, read_elsewhere
+    P = Program('cpu')
+    for kind, i, o in ((L.OP_CONV, -1, 5), (L.OP_RECORD, 5, 5), (L.OP_NOP, 5, 5), (L.OP_CONV, 5, 6), (L.OP_CONV, 6, 5), (L.OP_CONV, 5, 7),
+                       (L.OP_CONV, 7, 7)):
+        op = L.RompOp()
+        op.kind, op.in_buf, op.out_buf, op.res_buf = kind, i, o, L.BUF_NONE
+        P.emit(op, 'op%d' % len(P.ops), 0.0, 0.0)
+    assert read_elsewhere(P, 0, 5)                           # op 3, before the next writer (op 4): the NOP at 2 does not end the range
+    assert not read_elsewhere(P, 0, 5, but=(3,))             # the marker and the NOP do not read; op 5 reads the NEXT live range
+    assert read_elsewhere(P, 4, 5) and not read_elsewhere(P, 4, 5, but=(5,))
+    assert read_elsewhere(P, 5, 7)                           # op 6 runs in place: a reader first
+    assert not read_elsewhere(P, 5, 7, but=(6,)) and not read_elsewhere(P, 6, 7)
+
+
+def test_up_conv_with_another_reader_keeps_running(monkeypatch):
+    """plan.fuse_up_sums turns a 1x1 up-conv into a NOP only when NOTHING reads its output any more -- a fused BasicBlock counts
+    like any other reader."""
+    from romp_amd import lib as L
+    for v in ('ROMP_FUSE_BLOCKS', 'ROMP_FUSEUP'):
+        monkeypatch.delenv(v, raising=False)
+    P, x0, x1, up = _fuseup_program(False)
+    assert P.fused_ups == 1 and P.ops[2].kind == L.OP_NOP and P.flops[2] == 0.0
+    P, x0, x1, up = _fuseup_program(True)
+    kinds = [o.kind for o in P.ops]
+    assert kinds == [L.OP_CONV, L.OP_CONV, L.OP_CONV, L.OP_FUSEUP, L.OP_CONV, L.OP_NOP, L.OP_BBLOCK32], kinds
+    assert P.fused_ups == 1 and P.ops[6].res_buf == up.buf and P.flops[2] > 0.0 and P.bytes[2] > 0.0
+
+
+def test_basic_block_whose_intermediate_is_read_in_place_stays_two_convs(monkeypatch):
+    """plan.fuse_basic_blocks: the intermediate tensor of a fused block never reaches memory, so a later op that reads it -- here
+    one that also rewrites the buffer in place, which used to pass for the buffer's next writer -- keeps the block unfused."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, set_conv_math
+    monkeypatch.delenv('ROMP_FUSE_BLOCKS', raising=False)
+    for in_place in (False, True):
+        P = Program('cpu')
+        set_conv_math(P, 'f16x2')
+        a0 = P.conv('c0', Act(L.BUF_IMAGE, 32, 16, 16, 32), *_wsb(32, 32, 3), 3, 1, True)
+        a1 = P.conv('c1', a0, *_wsb(32, 32, 3), 3, 1, True)
+        P.conv('c2', a1, *_wsb(32, 32, 3), 3, 1, True, res=a0)
+        if in_place:
+            P.conv('again', a1, *_wsb(32, 32), 1, 1, True, out=a1)
+        P.op_array()
+        assert P.fused_blocks == (0 if in_place else 1)
+        assert [o.kind for o in P.ops[:3]] == ([L.OP_CONV] * 3 if in_place else [L.OP_CONV, L.OP_NOP, L.OP_BBLOCK32])
