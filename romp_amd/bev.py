@@ -8,7 +8,7 @@ and of the device-side steps of ``BEVv1.forward`` (bev/model.py:232-250) for BAS
 Network (HRNet-32 + BEV head), 3-D center parsing, per-person regression, SMPL-A / SMIL meshes,
 perspective projection, projection-based duplicate suppression and outlier removal
 (bev/post_parser.py:68-136,167-222) all run in libromp_hip.so.  Video mode (``-t``): ByteTrack-3D association on the host
-(tracker.py) + OneEuro filters on the device (temporal.py); ``--render_mesh``: the Sim3DR rasteriser (renderer.py).
+(tracker.py) or, with ``--device_tracker``, on the device (tracking.py) + OneEuro filters on the device (temporal.py); ``--render_mesh``: the Sim3DR rasteriser (renderer.py).
 Crowd mode (``--crowd``, bev/main.py:184-258, bev/split2process.py): a frame with W / H >= 2 is cut into overlapping crops that
 go through ONE batched pre-processing launch (csrc/crowd.hip), the network in chunks of ``max_batch``, one SMPL-A / SMIL call
 and a device merge (boundary exclusion, per-crop and full-frame suppression / outlier removal).  The reference turns crowd mode
@@ -67,6 +67,10 @@ def bev_settings(input_args=sys.argv[1:]):
     p.add_argument('--smil_path', type=str, default=osp.join(osp.expanduser('~'), '.romp', 'smil_packed_info.pth'))
     p.add_argument('--model_path', type=str, default=osp.join(osp.expanduser('~'), '.romp', 'BEV.pth'))
     p.add_argument('-t', '--temporal_optimize', action='store_true')
+    p.add_argument('--device_tracker', action='store_true',
+                   help='[romp_amd] with -t: ByteTrack-3D association on the device too (tracking.py): two launches and one download per '
+                        'frame instead of three downloads and the host tracker; same results while a source has seen at most 256 track '
+                        'ids (beyond that the host filter bank clears all its filters, the device one never does)')
     p.add_argument('--max_batch', type=int, default=32)
     p.add_argument('--conv_math', type=str, default='f16x2', choices=['f32', 'bf16x3', 'f16x2', 'all'],
                    help='[romp_amd] f32 MFMA only, or also the f32-accurate split-precision kernels (f16x2: 2 fp16 pieces; bf16x3; chosen by autotune)')
@@ -256,7 +260,9 @@ class BEV(nn.Module):
         self.result_keys = ['smpl_thetas', 'smpl_betas', 'cam', 'cam_trans', 'params_pred', 'center_confs', 'pred_batch_ids']
         if settings.temporal_optimize:                                                      # bev/main.py:117-121
             self.OE_filters = {}
-            if not settings.show_largest:
+            if not settings.show_largest and getattr(settings, 'device_tracker', False):
+                self.device_smoothers = {}                                                  # signal_ID -> tracking.TrackedSmoother
+            elif not settings.show_largest:
                 from .tracker import Tracker
                 self.tracker = Tracker(det_thresh=0.12, low_conf_det_thresh=0.05, track_buffer=60, match_thresh=300, frame_rate=30)
         if settings.render_mesh:                                                            # bev/main.py:112-114
@@ -281,6 +287,8 @@ class BEV(nn.Module):
             th, be, ca = (outputs[k][max_id:max_id + 1].contiguous().clone() for k in ('smpl_thetas', 'smpl_betas', 'cam'))
             outputs['smpl_thetas'], outputs['smpl_betas'], outputs['cam'] = bank.smooth([0], th, be, ca)
             return outputs
+        if getattr(self.settings, 'device_tracker', False):
+            return BEV._temporal_optimization_device(self, outputs, signal_ID, image_scale, depth_scale)
         cams = outputs['cam'].cpu().numpy()
         cam_trans = outputs['cam_trans'].cpu().numpy()
         det_confs = outputs['center_confs'].cpu().numpy()
@@ -295,6 +303,32 @@ class BEV(nn.Module):
         outputs['smpl_thetas'], outputs['smpl_betas'], outputs['cam'] = bank.smooth(tracked_ids, outputs['smpl_thetas'],
                                                                                     outputs['smpl_betas'], outputs['cam'])
         outputs['track_ids'] = np.array(tracked_ids).astype(np.int32)
+        return outputs
+
+    def _temporal_optimization_device(self, outputs, signal_ID, image_scale=128, depth_scale=30):
+        """--device_tracker: the association on the device as well (tracking.py): the tracking points are built there, one launch
+        tracks, one launch filters, every other entry is gathered with the padded device rows, and ONE download (count and ids) tells
+        how far to narrow them.  Each signal_ID has its own tracker state, ids counted from 1."""
+        from .tracking import TrackedSmoother, bev_tracking_points
+        if signal_ID not in self.device_smoothers:
+            if len(self.device_smoothers) > 100:
+                self.device_smoothers.clear()
+            self.device_smoothers[signal_ID] = TrackedSmoother(self.tdevice, getattr(self.settings, 'smooth_coeff', 3.), outputs['smpl_betas'].shape[1],
+                                                               det_thresh=0.12, low_conf_det_thresh=0.05, track_buffer=60, match_thresh=300,
+                                                               frame_rate=30)
+        sm = self.device_smoothers[signal_ID]
+        points = bev_tracking_points(outputs['cam'], outputs['cam_trans'], image_scale, depth_scale)
+        buf, _, _, rows, _, th, be, ca = sm.run(points, outputs['center_confs'].float(), outputs['smpl_thetas'], outputs['smpl_betas'], outputs['cam'])
+        rows = rows[0].long()
+        gathered = {key: outputs[key][rows] for key in self.result_keys if key not in ('smpl_thetas', 'smpl_betas', 'cam')}
+        counts, ids = sm.download(buf, 1, sm.capacity)                                      # the one synchronisation
+        n = int(counts[0])
+        if n == 0:
+            return None
+        for key, v in gathered.items():
+            outputs[key] = v[:n]
+        outputs['smpl_thetas'], outputs['smpl_betas'], outputs['cam'] = th[:n], be[:n], ca[:n]
+        outputs['track_ids'] = ids[0, :n].astype(np.int32)
         return outputs
 
     @torch.no_grad()

@@ -145,6 +145,12 @@ def load():
         'romp_fit_pose_prior': (C.c_int, [vp, i32, vp, vp, vp, i32, i32, f, f, vp, vp, vp, i32, vp, i32, vp]),
         'romp_fit_joints3d': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, f, f, vp, vp, vp,
                                         i32, vp, i32, vp]),
+        'romp_track_state_bytes': (C.c_int, [i32]),
+        'romp_track_init': (C.c_int, [vp, i32, i32, f, f, C.c_double, i32, C.c_double, vp]),
+        'romp_track_frames': (C.c_int, [vp, vp, vp, C.POINTER(C.c_int32), i32, vp, vp, vp, vp, vp, i32, vp]),
+        'romp_track_assign': (C.c_int, [vp, i32, i32, C.c_double, vp, vp]),
+        'romp_track_list': (C.c_int, [vp, vp, vp, vp]),
+        'romp_oneeuro_smooth_frames': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, f, vp, vp, vp, vp, vp, vp, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -185,6 +191,10 @@ SMPL_GRAD_EXPORTS = ['smpl_backward']
 FIT_EXPORTS = ['romp_fit_reproject', 'romp_fit_adam']
 # include/romp_hip_fit_priors.h: SMPLify's pose priors (max-mixture GMM, joint angles) and 3-D joint targets for the same fit
 FIT_PRIOR_EXPORTS = ['romp_fit_pose_prior', 'romp_fit_joints3d']
+# include/romp_hip_track.h: ByteTrack-3D association on the device (the tracker, its assignment alone, the track lists) and the
+# OneEuro filters over what it reported
+TRACK_EXPORTS = ['romp_track_state_bytes', 'romp_track_init', 'romp_track_frames', 'romp_track_assign', 'romp_track_list',
+                 'romp_oneeuro_smooth_frames']
 
 
 def has_bf16x3():

@@ -8,7 +8,8 @@ over (x, y, z, h)) and the two helpers of ``matching.py`` it calls (``linear_ass
 
 This is per-frame bookkeeping over <= 64 detections (a 64 x 64 cost matrix, 8 x 8 covariances): the reference runs it in
 numpy on the host between two network calls, and so does this module; the device work of the temporal mode is the OneEuro
-filtering (``temporal.py`` / csrc/temporal.hip).  Quirks are kept: the second association re-uses the HIGH-score detections
+filtering (``temporal.py`` / csrc/temporal.hip).  ``tracking.py`` / csrc/track.hip make the same decisions on the device
+(``BEV --device_tracker``); this module stays the default and the definition they are tested against.  Quirks are kept: the second association re-uses the HIGH-score detections
 (:77-79), a brand-new track is `activated` only on frame 1 (:233-235), duplicate removal compares the first two coordinates.
 
 The reference solves the assignment with ``lap.lapjv(cost, extend_cost=True, cost_limit=t)`` (third-party `lap`, not installed
