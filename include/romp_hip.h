@@ -221,8 +221,8 @@ int  romp_net_profile(romp_net* net, const float* image_nhwc, int B, float* cent
 /* Activation range scan (f16x2 range safety): runs the program op by op on `stream` and reports, for every op that writes an
  * arena buffer, max|x| (maxabs_out_host[n_ops]; H2 tensors decoded) and the number of non-finite values
  * (nonfinite_out_host[n_ops]) of the REGION the op wrote (its pixels x channel slice of B images) right after the op; 0 for ops
- * without an arena output.  saturated_out_host[n_ops] (may be NULL): saturation events each op reported (see romp_net_saturated;
- * the fused-block kernels run their counting builds during a scan).  The host (plan.assign_formats) keeps tensors whose range
+ * without an arena output.  saturated_out_host[n_ops] (may be NULL): saturation events each op reported (see romp_net_saturated).
+ * The host (plan.assign_formats) keeps tensors whose range
  * does not fit the fp16 pieces of ROMP_FMT_H2 in float32 and their consumers on the f32 / bf16x3 kernels; the kernels themselves
  * saturate at +-65504 instead of producing inf / NaN pieces.  Synchronises. */
 int  romp_net_range_scan(romp_net* net, const float* image_nhwc, int B, float* center_maps, float* params_maps_nhwc,

@@ -165,33 +165,33 @@ __global__ __launch_bounds__(256) void conv3d_kernel(Conv3dParams p, int B) {
     }
 }
 
-int launch_bev_pack(const float* fv, int fv_cs, const float* feats, int f_cs, float* out, int B, hipStream_t st) {
+int launch_bev_pack(const float* fv, int fv_cs, const float* feats, int f_cs, float* out, int B, const LaunchCtx& c) {
     const size_t total = (size_t)B * BM * 20 * BM;
-    hipLaunchKernelGGL(bev_pack_kernel, dim3(2048), dim3(256), 0, st, fv, fv_cs, feats, f_cs, out, total);
+    hipLaunchKernelGGL(bev_pack_kernel, dim3(2048), dim3(256), 0, c.st, fv, fv_cs, feats, f_cs, out, total);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
 
 int launch_bev_maps(const float* fv, int fv_cs, const float* bv, int bv_cs, const float* anchors_host, float* center3d,
-                    float* cam3d, int B, hipStream_t st) {
+                    float* cam3d, int B, const LaunchCtx& c) {
     Anchors an;
     for (int i = 0; i < BD; ++i) an.a[i] = anchors_host[i];
     const size_t total = (size_t)B * BVOX;
-    hipLaunchKernelGGL(bev_maps_kernel, dim3(4096), dim3(256), 0, st, fv, fv_cs, bv, bv_cs, an, center3d, cam3d, total);
+    hipLaunchKernelGGL(bev_maps_kernel, dim3(4096), dim3(256), 0, c.st, fv, fv_cs, bv, bv_cs, an, center3d, cam3d, total);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
 
 int launch_conv3d(int C, const float* w_host, const float* scale_host, const float* shift_host, int relu, const float* in,
-                  const float* res, float* out, int B, hipStream_t st) {
+                  const float* res, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(C == 1 || C == 3, "conv3d: %d channels unsupported", C);
     Conv3dParams p;
     p.in = in; p.res = res; p.out = out; p.relu = relu;
     for (int i = 0; i < C * C * 27; ++i) p.w[i] = w_host[i];
     for (int i = 0; i < C; ++i) { p.scale[i] = scale_host[i]; p.shift[i] = shift_host[i]; }
     const int grid = B * (BD / T3_D) * (BM / T3_H);
-    if (C == 1) hipLaunchKernelGGL(conv3d_kernel<1>, dim3(grid), dim3(256), 0, st, p, B);
-    else hipLaunchKernelGGL(conv3d_kernel<3>, dim3(grid), dim3(256), 0, st, p, B);
+    if (C == 1) hipLaunchKernelGGL(conv3d_kernel<1>, dim3(grid), dim3(256), 0, c.st, p, B);
+    else hipLaunchKernelGGL(conv3d_kernel<3>, dim3(grid), dim3(256), 0, c.st, p, B);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

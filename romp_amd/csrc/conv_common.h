@@ -41,7 +41,7 @@ struct ConvParams {
     unsigned res_bytes;       // (conv_h2x.hip, DS) bytes of the tensor at res + res_co (the downsample's input): num_records of its raw buffer
     unsigned in_bytes;        // (fused block kernel) bytes of the input tensor from in + in_co on: num_records of its raw buffer
     int relu_from;            // relu != 0: ReLU on output channels >= relu_from only (romp_op.relu_from; a multiple of 32)
-    int* sat;                 // saturation counter of the running net (conv_sat_counter(), may be nullptr): +1 per wave and work item that
+    int* sat;                 // saturation counter of the running net (LaunchCtx.sat, may be nullptr): +1 per wave and work item that
                               // clamped a value at +-65504 while splitting it into fp16 pieces (h2_sat): out-of-calibration activations
     int run_len;              // (fused block kernel, strip form) vertically consecutive tiles per run: a work item is a RUN, its tiles hand two
                               // rows of the intermediate on to each other (conv_h2c.h); tiles_y % run_len == 0
@@ -75,8 +75,7 @@ constexpr float H2_MAX = 65504.f;
 __device__ __forceinline__ float h2_sat(float x) { return __builtin_fminf(__builtin_fmaxf(x, -H2_MAX), H2_MAX); }
 // Saturation is OBSERVABLE: every site that clamps keeps a per-lane running max of |value before the clamp| (one
 // v_max3_f32 per two values) and reports once per wave and work item -- sat_report -- into the net's device counter
-// (romp_net_saturated; RompNet.saturated).  The two register-resident fused-block kernels (conv_h2b / conv_h2c.h), whose side work
-// is placed instruction by instruction, count in their checked builds only (romp_net_range_scan and ROMP_CHECK_FINITE=1 run those).
+// (romp_net_saturated; RompNet.saturated), which every launcher copies from its LaunchCtx into its parameters.
 __device__ __forceinline__ void sat_track(float& mx, float a, float b) { mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b))); }
 __device__ __forceinline__ void sat_report(int* counter, float mx) {
     if (counter && __builtin_amdgcn_ballot_w64(mx >= H2_MAX) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(counter, 1);
@@ -454,12 +453,13 @@ __device__ __forceinline__ void conv_epilogue_h2direct(const ConvParams& p, cons
 }
 
 typedef void (*conv_fn)(ConvParams);
-// math: 0 f32 MFMA, 1 bf16x3 (register-staged weights), 2 bf16x3 (LDS-DMA weight rows), 3 / 4 the same two for f16x2,
+// math (the values are visible through romp_conv_family_variants): 0 f32 MFMA, 1 bf16x3 (register-staged weights), 2 bf16x3 (LDS-DMA weight rows), 3 / 4 the same two for f16x2,
 // 8 f16x2 with register-resident weights (conv_h2r.hip), 9 its stride-2 form on parity planes (conv_h2s.hip),
 // 10 the input channels split across the workgroup's waves (conv_h2k.hip: single-image plans), 11 the 1x1 streamed-K GEMM form (conv_h2g.hip).  (5 / 6 / 7 were round 2's LDS-DMA pipeline kernels: never
 // faster than 3 / 4 / 8 inside the network, deleted in round 6; their measurements are in profiles/r02_*.)  threads: workgroup size (0 = 256, or 512 for the ping-pong kernels).
 // o4: the same kernel compiled for four workgroups per CU (128 VGPRs; named conv_h2o).
-struct ConvVariant { int ks, s, mt, nt, tw, ck; conv_fn fn; int lds; int th; int occ; int pp; int math; int threads; int o4; };
+enum ConvMath { MATH_F32 = 0, MATH_BX3 = 1, MATH_BXD = 2, MATH_H2 = 3, MATH_H2D = 4, MATH_H2R = 8, MATH_H2S = 9, MATH_H2K = 10, MATH_H2G = 11 };
+struct ConvVariant { int ks, s, mt, nt, tw, ck; conv_fn fn; int lds; int th; int occ; int pp; ConvMath math; int threads; int o4; };
 
 // per translation unit: its table of instantiated kernels
 ConvVariant* conv_variants_f32(int* n);

@@ -254,36 +254,21 @@ __global__ __launch_bounds__(256, 2) void fuseup_kernel(FupParams p) {
     sat_report(p.sat, sat_mx);
 }
 
-template <int CO, int NUP>
-static int launch_fup(FupParams& p, int B, hipStream_t st) {
-    using X = UCfg<CO, NUP>;
-    static bool attr = false;
-    static int num_cu = 256;
-    if (!attr) {                                               // (romp_net_create calls this path's set-up outside any stream capture)
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fuseup_kernel<CO, NUP>), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (p.out == nullptr) return ROMP_OK;                      // set-up only
-    ROMP_REQUIRE(p.n_direct <= X::MAXD, "fuseup: %d direct terms for a %d-channel output (at most %d)", p.n_direct, CO, X::MAXD);
-    ROMP_REQUIRE(p.H % X::TH == 0 && p.W % X::TW == 0, "fuseup: %dx%d is not a multiple of the %dx%d tile", p.H, p.W, X::TH, X::TW);
-    p.tiles_x = p.W / X::TW; p.tiles_y = p.H / X::TH; p.tiles_total = B * p.tiles_x * p.tiles_y;
-    const int cap = conv_wg_cap();
-    const int per_cu = (cap == 1 || 160 * 1024 / X::LDS_BYTES < 2) ? 1 : 2;
-    long grid = (long)num_cu * per_cu;
-    if (grid > p.tiles_total) grid = p.tiles_total;
-    hipLaunchKernelGGL((fuseup_kernel<CO, NUP>), dim3((unsigned)grid), dim3(256), X::LDS_BYTES, st, p);
-    ROMP_HIP_CHECK(hipGetLastError());
+// the kernel instantiations: (output channels, up-terms) and what the host needs of each
+struct FupKernel { int co, nup, maxd, th, tw, lds; void (*fn)(FupParams); };
+#define ROMP_FUP(CO_, NUP_) { CO_, NUP_, UCfg<CO_, NUP_>::MAXD, UCfg<CO_, NUP_>::TH, UCfg<CO_, NUP_>::TW, UCfg<CO_, NUP_>::LDS_BYTES, fuseup_kernel<CO_, NUP_> }
+static const FupKernel kFup[] = { ROMP_FUP(32, 1), ROMP_FUP(32, 2), ROMP_FUP(32, 3), ROMP_FUP(64, 1), ROMP_FUP(64, 2), ROMP_FUP(128, 1) };
+#undef ROMP_FUP
+
+int setup_fuseup() {
+    for (const FupKernel& k : kFup)
+        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     return ROMP_OK;
 }
 
-// `op`: ROMP_OP_FUSEUP (include/romp_hip.h).  terms[k]: the resolved tensors in op order -- the direct terms (term_shift 0) first, then
-// the up sources (term_shift 1, 2, ..).  terms == nullptr: one-time set-up of the kernel this op needs.
-int launch_fuseup(const romp_op& op, const FuseTerm* terms, float* out, int B, hipStream_t st) {
+// `op`: ROMP_OP_FUSEUP (include/romp_hip.h): the direct terms (term_shift 0) first, then the up sources (term_shift 1, 2, ..).
+// -> the kernel for it (`out`, may be nullptr) and its number of direct terms
+static int fup_kernel_for(const romp_op& op, const FupKernel** out, int* n_direct_out) {
     int n_direct = 0, n_up = 0;
     for (int k = 0; k < op.n_terms; ++k) {
         if (op.term_shift[k] == 0) { ROMP_REQUIRE(n_up == 0, "fuseup: direct terms come first"); ++n_direct; }
@@ -292,26 +277,46 @@ int launch_fuseup(const romp_op& op, const FuseTerm* terms, float* out, int B, h
     ROMP_REQUIRE(n_direct >= 1 && n_direct <= 3 && n_up >= 1 && n_up <= 3, "fuseup: %d direct + %d up terms", n_direct, n_up);
     ROMP_REQUIRE(op.weight_aux && op.scale_h2 && op.shift && (op.flags & ROMP_OPF_WAVE16), "fuseup: per-group f16x2 weight packs expected");
     ROMP_REQUIRE(op.out_fmt == ROMP_FMT_H2 && ((op.out_cstride | op.out_coff) & 7) == 0, "fuseup: H2 output expected");
+    for (int k = 0; k < op.n_terms; ++k) {
+        ROMP_REQUIRE(op.term_fmt[k] == ROMP_FMT_H2 && ((op.term_cstride[k] | op.term_coff[k]) & 7) == 0, "fuseup: term %d must be an octet-aligned H2 tensor", k);
+        const int u = k - n_direct;
+        ROMP_REQUIRE(u < 0 || (op.term_cstride[k] == (op.Cout << (u + 1)) && op.term_coff[k] == 0), "fuseup: up source %d must be a dense %d-channel tensor", u, op.Cout << (u + 1));
+    }
+    const FupKernel* f = nullptr;
+    for (const FupKernel& k : kFup)
+        if (k.co == op.Cout && k.nup == n_up) f = &k;
+    ROMP_REQUIRE(f, "fuseup: no kernel for %d channels with %d up-terms", op.Cout, n_up);
+    ROMP_REQUIRE(n_direct <= f->maxd, "fuseup: %d direct terms for a %d-channel output (at most %d)", n_direct, f->co, f->maxd);
+    ROMP_REQUIRE(op.H % f->th == 0 && op.W % f->tw == 0, "fuseup: %dx%d is not a multiple of the %dx%d tile", op.H, op.W, f->th, f->tw);
+    if (out) *out = f;
+    if (n_direct_out) *n_direct_out = n_direct;
+    return ROMP_OK;
+}
+int check_fuseup(const romp_op& op) { return fup_kernel_for(op, nullptr, nullptr); }
+
+// terms[k]: the resolved tensors in op order
+int launch_fuseup(const romp_op& op, const FuseTerm* terms, float* out, int B, const LaunchCtx& c) {
+    const FupKernel* f = nullptr;
+    int n_direct = 0;
+    { const int rc = fup_kernel_for(op, &f, &n_direct); if (rc) return rc; }
     FupParams p;
     memset(&p, 0, sizeof(p));
     p.n_direct = n_direct;
     for (int k = 0; k < op.n_terms; ++k) {
-        ROMP_REQUIRE(op.term_fmt[k] == ROMP_FMT_H2 && ((op.term_cstride[k] | op.term_coff[k]) & 7) == 0, "fuseup: term %d must be an octet-aligned H2 tensor", k);
-        if (k < n_direct) { p.dt[k] = terms ? terms[k].ptr : nullptr; p.d_cs[k] = op.term_cstride[k]; }
-        else {
-            const int u = k - n_direct;
-            ROMP_REQUIRE(op.term_cstride[k] == (op.Cout << (u + 1)) && op.term_coff[k] == 0, "fuseup: up source %d must be a dense %d-channel tensor", u, op.Cout << (u + 1));
-            p.ux[u] = terms ? terms[k].ptr : nullptr; p.u_cs[u] = op.term_cstride[k];
-        }
+        if (k < n_direct) { p.dt[k] = terms[k].ptr; p.d_cs[k] = op.term_cstride[k]; }
+        else { p.ux[k - n_direct] = terms[k].ptr; p.u_cs[k - n_direct] = op.term_cstride[k]; }
     }
     p.uw = reinterpret_cast<const uint4*>(op.weight_aux); p.us = op.scale_h2; p.ub = op.shift;
     p.out = out; p.out_cs = op.out_cstride; p.out_co = op.out_coff;
     p.H = op.H; p.W = op.W; p.relu = op.relu; p.act_scale = ldexpf(1.f, op.act_shift);
-    p.sat = conv_sat_counter();
-#define ROMP_FUP(CO_, NUP_) if (op.Cout == CO_ && n_up == NUP_) return launch_fup<CO_, NUP_>(p, B, st)
-    ROMP_FUP(32, 1); ROMP_FUP(32, 2); ROMP_FUP(32, 3); ROMP_FUP(64, 1); ROMP_FUP(64, 2); ROMP_FUP(128, 1);
-#undef ROMP_FUP
-    ROMP_REQUIRE(false, "fuseup: no kernel for %d channels with %d up-terms", op.Cout, n_up);
+    p.sat = c.sat;
+    p.tiles_x = p.W / f->tw; p.tiles_y = p.H / f->th; p.tiles_total = B * p.tiles_x * p.tiles_y;
+    const int per_cu = (c.wg_cap == 1 || 160 * 1024 / f->lds < 2) ? 1 : 2;
+    long grid = (long)device().num_cu * per_cu;
+    if (grid > p.tiles_total) grid = p.tiles_total;
+    hipLaunchKernelGGL(f->fn, dim3((unsigned)grid), dim3(256), f->lds, c.st, p);
+    ROMP_HIP_CHECK(hipGetLastError());
+    return ROMP_OK;
 }
 
 }  // namespace romp

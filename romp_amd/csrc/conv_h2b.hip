@@ -474,14 +474,19 @@ __global__ __launch_bounds__(256, 1) void bblock32_kernel(ConvParams p) {
 #undef SIDE_PIN
 }
 
-// `op` is the block's SECOND conv (its residual is the block input x, its output y); `op1` the first (weights / scale / shift).
-int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, hipStream_t st) {
-    {   // two implementations: this file's (v1: 16x16 tiles, one wave per SIMD) and conv_h2c.h's row-pipelined one (two waves per SIMD)
-        // The plan decides (plan.fuse_basic_blocks): the row-pipelined
-        // kernel needs the per-wave weight packs, announced by ROMP_OPF_WAVE16 -- weight_aux alone may just as well be the bf16x3 pack
-        // of conv_math='all' (a single-image 'all' plan ran the row kernel on bf16x3 bytes).
-        if ((op1.flags & op.flags & ROMP_OPF_WAVE16) && op.H % 8 == 0) return launch_bblock32r(op1, op, x, y, B, queue, st);
-    }
+int setup_bblock32() {
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bblock32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BCfg::LDS_BYTES));
+    return ROMP_OK;
+}
+
+// Two implementations: this file's (v1: 16x16 tiles, one wave per SIMD) and conv_h2c.h's row-pipelined one (two waves per SIMD).
+// The plan decides (plan.fuse_basic_blocks): the row-pipelined kernel needs the per-wave weight packs, announced by
+// ROMP_OPF_WAVE16 -- weight_aux alone may just as well be the bf16x3 pack of conv_math='all' (a single-image 'all' plan
+// ran the row kernel on bf16x3 bytes).
+static bool bblock32_rows(const romp_op& op1, const romp_op& op) { return (op1.flags & op.flags & ROMP_OPF_WAVE16) && op.H % 8 == 0; }
+
+int check_bblock32(const romp_op& op1, const romp_op& op) {
+    if (bblock32_rows(op1, op)) return check_bblock32r(op1, op);
     ROMP_REQUIRE(op.ksize == 3 && op.stride == 1 && op.Cin == 32 && op.Cout == 32 && op.cin_pad == 32 && op.cout_pad == 32 && op.groups == 1 &&
                  op1.ksize == 3 && op1.stride == 1 && op1.Cin == 32 && op1.Cout == 32 && op1.cin_pad == 32 && op1.cout_pad == 32 && op1.groups == 1,
                  "bblock32: two 3x3 stride-1 32 -> 32 convs expected");
@@ -491,21 +496,13 @@ int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float
     ROMP_REQUIRE(op.H % 16 == 0 && op.W % 16 == 0 && op1.H == op.H && op1.W == op.W, "bblock32: %dx%d is not a multiple of the 16x16 tile", op.H, op.W);
     ROMP_REQUIRE(op1.in_cstride == op.res_cstride && op1.in_coff == op.res_coff && ((op1.in_cstride | op1.in_coff | op.out_cstride | op.out_coff) & 7) == 0,
                  "bblock32: the residual must be the block input, octet aligned");
-    static bool attr = false;
-    static float* zero = nullptr;                              // 256 bytes of zeros: what out-of-image lanes of the halo DMA fetch
-    static int num_cu = 256;
-    if (!attr) {                                               // (romp_net_create calls this path's setup outside any stream capture: bblock_init)
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bblock32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BCfg::LDS_BYTES));
-        ROMP_HIP_CHECK(hipMalloc((void**)&zero, 256));
-        ROMP_HIP_CHECK(hipMemset(zero, 0, 256));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (x == nullptr && y == nullptr) return ROMP_OK;          // set-up only
+    return ROMP_OK;
+}
+
+// `op` is the block's SECOND conv (its residual is the block input x, its output y); `op1` the first (weights / scale / shift).
+int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, const LaunchCtx& c) {
+    if (bblock32_rows(op1, op)) return launch_bblock32r(op1, op, x, y, B, queue, c);
+    { const int rc = check_bblock32(op1, op); if (rc) return rc; }
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.in = x; p.res = x; p.out = y;
@@ -513,13 +510,13 @@ int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float
     p.wh = reinterpret_cast<const uint4*>(op.weight_h2);
     p.scale = op1.scale_h2; p.w = op1.shift;                   // conv1's epilogue scale / shift (see the kernel's header)
     p.scale_h = op.scale_h2; p.shift = op.shift;
-    p.zero = zero;
+    p.zero = device().zero;                                    // what out-of-image lanes of the halo DMA fetch
     p.act_scale = ldexpf(1.f, op.act_shift);
     p.inv_act_scale = ldexpf(1.f, -op.act_shift);
     p.in_h2 = p.out_h2 = p.res_h2 = 1;
     p.queue = queue;
-    p.trace = conv_trace_arm(st);
-    p.sat = conv_sat_counter();
+    p.trace = conv_trace_arm(c.st);
+    p.sat = c.sat;
     {
         const unsigned long long bytes = ((unsigned long long)B * op.H * op.W * op1.in_cstride - op1.in_coff) * 4ull;
         ROMP_REQUIRE(bytes < 0x80000000ull, "bblock32: input tensor of %llu bytes: beyond the 31-bit offsets of the halo fetch", bytes);
@@ -539,10 +536,10 @@ int launch_bblock32(const romp_op& op1, const romp_op& op, const float* x, float
     p.pad_h = p.pad_w = 1;
     p.out_rs = op.out_rstride > 0 ? op.out_rstride : p.Wo * op.out_cstride;
     p.out_bs = op.out_bstride > 0 ? op.out_bstride : p.Ho * p.Wo * op.out_cstride;
-    long grid = num_cu;                                        // one workgroup per CU
+    long grid = device().num_cu;                               // one workgroup per CU
     if (grid > p.tiles_total) grid = p.tiles_total;
     if (p.n_queues == 8) grid = grid >= 8 ? (grid / 8) * 8 : 8;
-    hipLaunchKernelGGL(bblock32_kernel, dim3((unsigned)grid), dim3(256), BCfg::LDS_BYTES, st, p);
+    hipLaunchKernelGGL(bblock32_kernel, dim3((unsigned)grid), dim3(256), BCfg::LDS_BYTES, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

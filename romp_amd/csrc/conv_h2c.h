@@ -739,10 +739,15 @@ __global__ __launch_bounds__(256, RCfg<C>::WG_PER_CU) void bblockr_kernel(ConvPa
 #undef SIDE_PIN
 }
 
-// `op` is the block's SECOND conv (its residual is the block input x, its output y); `op1` the first.  Their per-wave weight packs
-// (plan.pack_h2_wave16) are in `weight_aux`.
 template <int C>
-static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, hipStream_t st) {
+static int setup_bblockr() {
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bblockr_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, RCfg<C>::LDS_BYTES));
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bblockr_kernel<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, RCfg<C>::LDS_BYTES));
+    return ROMP_OK;
+}
+
+template <int C>
+static int check_bblockr(const romp_op& op1, const romp_op& op) {
     using X = RCfg<C>;
     ROMP_REQUIRE(op.ksize == 3 && op.stride == 1 && op.Cin == C && op.Cout == C && op.groups == 1 &&
                  op1.ksize == 3 && op1.stride == 1 && op1.Cin == C && op1.Cout == C && op1.groups == 1,
@@ -754,21 +759,17 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     ROMP_REQUIRE(op.H % X::TH == 0 && op.W % X::TW == 0 && op1.H == op.H && op1.W == op.W, "bblock%d: %dx%d is not a multiple of the 8x16 tile", C, op.H, op.W);
     ROMP_REQUIRE(op1.in_cstride == op.res_cstride && op1.in_coff == op.res_coff && ((op1.in_cstride | op1.in_coff | op.out_cstride | op.out_coff) & 7) == 0,
                  "bblock%d: the residual must be the block input, octet aligned", C);
-    static bool attr = false;
-    static int num_cu = 256;
+    return ROMP_OK;
+}
+
+// `op` is the block's SECOND conv (its residual is the block input x, its output y); `op1` the first.  Their per-wave weight packs
+// (plan.pack_h2_wave16) are in `weight_aux`.
+template <int C>
+static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, const LaunchCtx& c) {
+    using X = RCfg<C>;
+    { const int rc = check_bblockr<C>(op1, op); if (rc) return rc; }
     using KernelFn = void (*)(ConvParams);
     const KernelFn fn = bblockr_kernel<C>, fn_strip = bblockr_kernel<C, true>;
-    if (!attr) {                                               // (romp_net_create calls this path's set-up outside any stream capture)
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_strip), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (x == nullptr && y == nullptr) return ROMP_OK;          // set-up only
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.in = x; p.res = x; p.out = y;
@@ -780,8 +781,8 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     p.inv_act_scale = ldexpf(1.f, -op.act_shift);
     p.in_h2 = p.out_h2 = p.res_h2 = 1;
     p.queue = queue;
-    p.trace = conv_trace_arm(st);
-    p.sat = conv_sat_counter();
+    p.trace = conv_trace_arm(c.st);
+    p.sat = c.sat;
     {
         const unsigned long long bytes = ((unsigned long long)B * op.H * op.W * op1.in_cstride - op1.in_coff) * 4ull;
         ROMP_REQUIRE(bytes < 0x80000000ull, "bblock%d: input tensor of %llu bytes: beyond the 31-bit offsets of the halo fetch", C, bytes);
@@ -801,8 +802,7 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     p.pad_h = p.pad_w = 1;
     p.out_rs = op.out_rstride > 0 ? op.out_rstride : p.Wo * op.out_cstride;
     p.out_bs = op.out_bstride > 0 ? op.out_bstride : p.Ho * p.Wo * op.out_cstride;
-    const int cap = conv_wg_cap();
-    const long grid_max = (long)num_cu * ((cap > 0 && cap < X::WG_PER_CU) ? cap : X::WG_PER_CU);
+    const long grid_max = (long)device().num_cu * ((c.wg_cap > 0 && c.wg_cap < X::WG_PER_CU) ? c.wg_cap : X::WG_PER_CU);
     // The strip form (RCfg): runs of L vertically consecutive tiles, L a divisor of the tile rows.  In units of one plain tile a
     // carrying tile costs ~0.85 and a run's first ~1.05 (the prologue is not hand-scheduled); a workgroup takes ceil(runs / grid) runs
     // against ceil(tiles / grid) plain tiles: the cheapest estimate wins, the plain kernel if none beats it (small batches: L = 1)
@@ -812,8 +812,8 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
         double best = (double)rounds(p.tiles_total);
         for (int l = 2; l <= p.tiles_y; ++l) {
             if (p.tiles_y % l) continue;
-            const double c = (double)rounds(p.tiles_total / l) * (1.05 + 0.85 * (l - 1));
-            if (c < best - 1e-9) { best = c; L = l; }
+            const double cost = (double)rounds(p.tiles_total / l) * (1.05 + 0.85 * (l - 1));
+            if (cost < best - 1e-9) { best = cost; L = l; }
         }
         // env ROMP_BBLOCK_RUN (tests, A/B runs; read at every launch -- launches are captured into the net's graph once): 0 = never the
         // strip form, n > 1 = runs of n tiles wherever n divides the tile rows (the plain kernel elsewhere)
@@ -835,7 +835,7 @@ static int launch_bblockr(const romp_op& op1, const romp_op& op, const float* x,
     long grid = grid_max;
     if (grid > items) grid = items;
     if (p.n_queues == 8) grid = grid >= 8 ? (grid / 8) * 8 : 8;
-    hipLaunchKernelGGL(f, dim3((unsigned)grid), dim3(256), X::LDS_BYTES, st, p);
+    hipLaunchKernelGGL(f, dim3((unsigned)grid), dim3(256), X::LDS_BYTES, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

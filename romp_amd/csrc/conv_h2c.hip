@@ -5,8 +5,10 @@
 
 namespace romp {
 
-int launch_bblock64(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, hipStream_t st) {
-    return launch_bblockr<64>(op1, op, x, y, B, queue, st);
+int setup_bblock64() { return setup_bblockr<64>(); }
+int check_bblock64(const romp_op& op1, const romp_op& op) { return check_bblockr<64>(op1, op); }
+int launch_bblock64(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, const LaunchCtx& c) {
+    return launch_bblockr<64>(op1, op, x, y, B, queue, c);
 }
 
 }  // namespace romp

@@ -4,8 +4,10 @@
 
 namespace romp {
 
-int launch_bblock32r(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, hipStream_t st) {
-    return launch_bblockr<32>(op1, op, x, y, B, queue, st);
+int setup_bblock32r() { return setup_bblockr<32>(); }
+int check_bblock32r(const romp_op& op1, const romp_op& op) { return check_bblockr<32>(op1, op); }
+int launch_bblock32r(const romp_op& op1, const romp_op& op, const float* x, float* y, int B, int* queue, const LaunchCtx& c) {
+    return launch_bblockr<32>(op1, op, x, y, B, queue, c);
 }
 
 }  // namespace romp

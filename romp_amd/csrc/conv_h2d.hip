@@ -17,10 +17,10 @@ __global__ __launch_bounds__(256, 4) void conv_h2do4_kernel(ConvParams p) {
 }
 #define ROMP_CONV_VARIANT_H2DO4(KS, S, MT, NT, TW, CK)                                \
     { KS, S, MT, NT, TW, CK, conv_h2do4_kernel<KS, S, MT, NT, TW, CK>,                \
-      SplitCfg<2, KS, S, MT, NT, TW, CK>::LDS_BYTES_DMA, ConvCfg<KS, S, MT, NT, TW, CK>::TH, 0, 0, 4, 0, 1 }
+      SplitCfg<2, KS, S, MT, NT, TW, CK>::LDS_BYTES_DMA, ConvCfg<KS, S, MT, NT, TW, CK>::TH, 0, 0, MATH_H2D, 0, 1 }
 #define ROMP_CONV_VARIANT_H2D(KS, S, MT, NT, TW, CK)                                  \
     { KS, S, MT, NT, TW, CK, conv_h2d_kernel<KS, S, MT, NT, TW, CK>,                  \
-      SplitCfg<2, KS, S, MT, NT, TW, CK>::LDS_BYTES_DMA, ConvCfg<KS, S, MT, NT, TW, CK>::TH, 0, 0, 4, 0 }
+      SplitCfg<2, KS, S, MT, NT, TW, CK>::LDS_BYTES_DMA, ConvCfg<KS, S, MT, NT, TW, CK>::TH, 0, 0, MATH_H2D, 0 }
 static ConvVariant kVariantsH2d[] = {
     ROMP_CONV_VARIANT_H2D(3, 1, 2, 2, 16, 16), ROMP_CONV_VARIANT_H2D(3, 1, 2, 2, 32, 16),
     ROMP_CONV_VARIANT_H2D(3, 1, 2, 1, 16, 16), ROMP_CONV_VARIANT_H2D(3, 1, 2, 1, 32, 16),

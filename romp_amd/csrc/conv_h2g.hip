@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2g_kernel(ConvParams p) {
 
 #define ROMP_CONV_VARIANT_H2G(KS, P, NS, TW, S, KSUB)                                                                \
     { KS, S, P, NS, TW, 32 * KSUB, conv_h2g_kernel<KS, P, NS, TW, S, KSUB>, GCfg<KS, P, NS, TW, S, KSUB>::LDS_BYTES, \
-      GCfg<KS, P, NS, TW, S, KSUB>::C::TH, 0, 0, 11, 256 }
+      GCfg<KS, P, NS, TW, S, KSUB>::C::TH, 0, 0, MATH_H2G, 256 }
 
 static ConvVariant kVariantsH2g[] = {
     // 128 pixels x 128 channels, 64 x 128, 256 x 64, 128 x 64 (64-channel outputs: layer1's conv1, HRNet's transition-free 1x1s)

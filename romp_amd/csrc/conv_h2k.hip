@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2k_kernel(ConvParams p) {
 
 // math 10: the input channels split across the workgroup's waves; `ck` = 64 (a super-stage)
 #define ROMP_CONV_VARIANT_H2K(KS, S, P, TW)                                                            \
-    { KS, S, P, 1, TW, 64, conv_h2k_kernel<KS, S, P, TW>, KCfg<KS, S, P, TW>::LDS_BYTES, KCfg<KS, S, P, TW>::C::TH, 0, 0, 10, 256 }
+    { KS, S, P, 1, TW, 64, conv_h2k_kernel<KS, S, P, TW>, KCfg<KS, S, P, TW>::LDS_BYTES, KCfg<KS, S, P, TW>::C::TH, 0, 0, MATH_H2K, 256 }
 
 static ConvVariant kVariantsH2k[] = { ROMP_CONV_VARIANT_H2K(3, 1, 1, 16), ROMP_CONV_VARIANT_H2K(3, 1, 2, 16), ROMP_CONV_VARIANT_H2K(1, 1, 1, 16),
                                       ROMP_CONV_VARIANT_H2K(3, 2, 1, 16) };

@@ -297,10 +297,10 @@ __global__ __launch_bounds__(256, 2) void conv_h2r_kernel(ConvParams p) {
 
 #define ROMP_CONV_VARIANT_H2R(P, NS, TW)                                                               \
     { 3, 1, P, NS, TW, 16, conv_h2r_kernel<P, NS, TW>, RCfg<P, NS, TW>::LDS_BYTES,                     \
-      RCfg<P, NS, TW>::C::TH, 0, 0, 8, 256 }
+      RCfg<P, NS, TW>::C::TH, 0, 0, MATH_H2R, 256 }
 #define ROMP_CONV_VARIANT_H2R32(P, NS, TW)                                                             \
     { 3, 1, P, NS, TW, 32, conv_h2r_kernel<P, NS, TW, 2>, RCfg<P, NS, TW, 2>::LDS_BYTES,               \
-      RCfg<P, NS, TW, 2>::C::TH, 0, 0, 8, 256 }
+      RCfg<P, NS, TW, 2>::C::TH, 0, 0, MATH_H2R, 256 }
 
 static ConvVariant kVariantsH2r[] = {
     ROMP_CONV_VARIANT_H2R(2, 1, 16), ROMP_CONV_VARIANT_H2R(2, 2, 16), ROMP_CONV_VARIANT_H2R(2, 4, 16), ROMP_CONV_VARIANT_H2R(1, 4, 16),

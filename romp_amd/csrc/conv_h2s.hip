@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void conv_h2s_kernel(ConvParams p) {
 
 #define ROMP_CONV_VARIANT_H2S(P, NS, TW)                                                               \
     { 3, 2, P, NS, TW, 16, conv_h2s_kernel<P, NS, TW>, SCfg<P, NS, TW>::LDS_BYTES,                     \
-      SCfg<P, NS, TW>::C::TH, 0, 0, 9, 256 }
+      SCfg<P, NS, TW>::C::TH, 0, 0, MATH_H2S, 256 }
 
 // (P = 2, NS = 2 needs 2 x 48 KB of stage buffers: one workgroup per CU; on offer for the deep-channel layers all the same)
 static ConvVariant kVariantsH2s[] = {

@@ -270,7 +270,15 @@ __global__ __launch_bounds__(256, 1) void seam1x1_kernel(ConvParams p) {
 // `opa`: the 64 -> 256 conv (+ residual + ReLU), `opb`: the 256 -> 64 conv (+ ReLU) reading its output.  `opd` (or nullptr): the
 // 64 -> 256 downsample conv whose output WAS opa's residual (ROMP_OPF_SEAM_DS on opb; plan.fuse_bottleneck_seams); `x` is then
 // opd's INPUT tensor (64 channels)
-int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, const float* m, const float* x, float* t, float* u, int B, hipStream_t st) {
+int setup_seam1x1() {
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(0)));
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(1)));
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(0)));
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(1)));
+    return ROMP_OK;
+}
+
+int check_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd) {
     ROMP_REQUIRE(opa.ksize == 1 && opa.stride == 1 && opa.Cin == 64 && opa.Cout == 256 && opa.groups == 1 && opa.relu &&
                  opb.ksize == 1 && opb.stride == 1 && opb.Cin == 256 && opb.Cout == 64 && opb.groups == 1 && opb.relu,
                  "seam1x1: a 1x1 64 -> 256 conv + residual + ReLU followed by a 1x1 256 -> 64 conv + ReLU expected");
@@ -278,7 +286,7 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
                  "seam1x1: per-group f16x2 weight packs (ROMP_OPF_WAVE16) expected");
     ROMP_REQUIRE(opa.in_fmt == ROMP_FMT_H2 && opa.res_fmt == ROMP_FMT_H2 && opa.out_fmt == ROMP_FMT_H2 && opb.in_fmt == ROMP_FMT_H2 &&
                  opb.out_fmt == ROMP_FMT_H2 && opa.act_shift == opb.act_shift, "seam1x1: H2 tensors expected");
-    ROMP_REQUIRE(((long)B * opa.H * opa.W) % XCfg::N == 0 && opa.H == opb.H && opa.W == opb.W, "seam1x1: pixel count not a multiple of 64");
+    ROMP_REQUIRE(opa.H == opb.H && opa.W == opb.W, "seam1x1: pixel count not a multiple of 64");
     ROMP_REQUIRE(((opa.in_cstride | opa.in_coff | opa.res_cstride | opa.res_coff | opa.out_cstride | opa.out_coff | opb.out_cstride | opb.out_coff) & 7) == 0 &&
                  opa.out_rstride == 0 && opa.out_bstride == 0 && opb.out_rstride == 0 && opb.out_bstride == 0, "seam1x1: dense, octet-aligned tensors expected");
     if (opd)
@@ -286,21 +294,13 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
                      opd->weight_aux && opd->scale_h2 && (opd->flags & ROMP_OPF_WAVE16) && opd->in_fmt == ROMP_FMT_H2 && opd->act_shift == opa.act_shift &&
                      opd->H == opa.H && opd->W == opa.W && ((opd->in_cstride | opd->in_coff) & 7) == 0 && opd->out_buf == opa.res_buf,
                      "seam1x1: the folded downsample must be a plain 1x1 64 -> 256 conv on an H2 tensor whose output was the residual");
-    static bool attr = false;
-    static int num_cu = 256;
-    if (!attr) {
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(0)));
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(1)));
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(0)));
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(seam1x1_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, XCfg::lds_bytes(1)));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (m == nullptr && t == nullptr) return ROMP_OK;          // set-up only
+    return ROMP_OK;
+}
+
+int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, const float* m, const float* x, float* t, float* u, int B, const LaunchCtx& c) {
+    { const int rc = check_seam1x1(opa, opb, opd); if (rc) return rc; }
+    ROMP_REQUIRE(((long)B * opa.H * opa.W) % XCfg::N == 0, "seam1x1: pixel count not a multiple of 64");
+    const hipStream_t st = c.st;
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.in = m; p.res = x; p.out = t; p.out2 = u;
@@ -309,7 +309,7 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
     p.scale = opa.scale_h2; p.w = opa.shift;
     p.scale_h = opb.scale_h2; p.shift = opb.shift;
     p.act_scale = ldexpf(1.f, opa.act_shift);
-    p.sat = conv_sat_counter();
+    p.sat = c.sat;
     {
         const unsigned long long bytes = ((unsigned long long)B * opa.H * opa.W * opa.in_cstride - opa.in_coff) * 4ull;
         ROMP_REQUIRE(bytes < 0x80000000ull, "seam1x1: input tensor of %llu bytes: beyond the 31-bit offsets of the DMA", bytes);
@@ -328,7 +328,7 @@ int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, c
     p.out_cs = opa.out_cstride; p.out_co = opa.out_coff;
     p.out2_cs = opb.out_cstride; p.out2_co = opb.out_coff;
     p.tiles_total = (int)(((long)B * opa.H * opa.W) / XCfg::N);
-    long grid = num_cu;
+    long grid = device().num_cu;
     if (grid > p.tiles_total) grid = p.tiles_total;
     const char* drain = getenv("ROMP_SEAM_FULL_DRAIN");       // the full-drain builds: the tests' reference for the counted waits
     if (drain && atoi(drain)) {

@@ -1,6 +1,7 @@
 // conv_mfma.hip -- dispatch of the NHWC float32 convolution kernels (conv_f32.hip: exact-f32 MFMA; conv_bx3.hip /
 // conv_h2.hip / conv_h2d.hip: split-precision kernels on the 16-bit matrix pipe) + the naive bring-up cross-check.
 #include "conv_common.h"
+#include <mutex>
 #include <vector>
 
 namespace romp {
@@ -45,38 +46,27 @@ __attribute__((weak)) ConvVariant* conv_variants_bx3(int* n) { *n = 0; return nu
 static std::vector<ConvVariant> kVariants;
 static int kNumVariants = 0;
 static void collect_variants() {
-    if (kNumVariants) return;
-    int n = 0;
-    ConvVariant* t = conv_variants_f32(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_bx3(&n); if (n) kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2d(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2r(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2s(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2k(&n); kVariants.insert(kVariants.end(), t, t + n);
-    t = conv_variants_h2g(&n); kVariants.insert(kVariants.end(), t, t + n);      // (appended last: the indices of older variants do not move)
-    kNumVariants = (int)kVariants.size();
+    static const bool once = [] {
+        int n = 0;
+        ConvVariant* t = conv_variants_f32(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_bx3(&n); if (n) kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2d(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2r(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2s(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2k(&n); kVariants.insert(kVariants.end(), t, t + n);
+        t = conv_variants_h2g(&n); kVariants.insert(kVariants.end(), t, t + n);      // (appended last: the indices of older variants do not move)
+        kNumVariants = (int)kVariants.size();
+        return true;
+    }();
+    (void)once;
 }
-static bool g_attr_done = false;
-static int g_num_cu = 256;
-static int* g_queue_scratch = nullptr;      // for romp_conv_forward callers without an arena
-static float* g_zero = nullptr;             // 256 bytes of zeros (out-of-image lanes of LDS-DMA pixel fetches)
-// Per HOST THREAD: the executor names its net's counter / cap right before it enqueues on that thread, so two nets driven from two
-// threads (RompNet.twin, ROMP_PIPE_NETS=2, a host with one net per thread) never see each other's values.
-static thread_local int* g_sat = nullptr;   // saturation counter of the net being run (conv_set_sat_counter), or nullptr
-static thread_local bool g_sat_checked = false;          // run the counting builds of the fused-block kernels (romp_net_range_scan, ROMP_CHECK_FINITE=1)
-static unsigned long long* g_trace = nullptr;   // env ROMP_CONV_TRACE=1: per-wave phase stamps of the most recent split-precision conv launch
 
 static const int kMaxLds = 160 * 1024;
 
-static int ensure_attrs() {
-    if (g_attr_done) return ROMP_OK;
+// this unit's part of device_init: LDS limits and occupancies of the generic conv variants
+static int setup_conv_variants() {
     collect_variants();
-    int dev = 0;
-    ROMP_HIP_CHECK(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    g_num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     for (int i = 0; i < kNumVariants; ++i) {
         if (kVariants[i].lds > kMaxLds) continue;
         if (kVariants[i].lds > 48 * 1024)
@@ -87,35 +77,49 @@ static int ensure_attrs() {
                                                                     kVariants[i].threads ? kVariants[i].threads : (kVariants[i].pp ? 512 : 256), kVariants[i].lds));
         kVariants[i].occ = occ > 0 ? occ : 1;
     }
-    ROMP_HIP_CHECK(hipMalloc((void**)&g_queue_scratch, QUEUE_INTS * sizeof(int)));
-    ROMP_HIP_CHECK(hipMalloc((void**)&g_zero, 256));
-    ROMP_HIP_CHECK(hipMemset(g_zero, 0, 256));
-    { const char* e = getenv("ROMP_CONV_TRACE");
-      if (e && atoi(e)) ROMP_HIP_CHECK(hipMalloc((void**)&g_trace, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long))); }
-    g_attr_done = true;
     return ROMP_OK;
 }
 
-// The executor (net.hip) names the running net's counter before it enqueues; every launcher copies it into its parameters.
-void conv_set_sat_counter(int* counter, bool checked_fused) { g_sat = counter; g_sat_checked = checked_fused; }
-int* conv_sat_counter() { return g_sat; }
-static thread_local int g_fused_cap = 0;    // workgroups per CU the fused kernels may take (0: all they can); set with the net's wg_cap
-void conv_set_wg_cap(int cap) { g_fused_cap = cap; }
-int conv_wg_cap() { return g_fused_cap; }
-bool conv_sat_checked() { return g_sat_checked; }
+static DeviceInfo g_dev;
+const DeviceInfo& device() { return g_dev; }
 
-// One-time per-process setup (LDS attributes, occupancy, scratch queue).  romp_net_create calls it so
-// that it never runs inside a stream capture (hipMalloc / hipFuncSetAttribute are illegal there).
-int conv_init() { return ensure_attrs(); }
+// One device per process (the design: one process per GPU, torch.distributed over RCCL): limits, CU count, zero page and occupancies
+// are kept per PROCESS.  A net on another device would silently run with the first device's, so it is refused.  A pointer
+// that a failed attempt allocated is kept for the retry.
+int device_init() {
+    static std::mutex mu;
+    static int device = -1;                 // >= 0: set up, for that device
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = -1;
+    ROMP_HIP_CHECK(hipGetDevice(&dev));
+    ROMP_REQUIRE(device < 0 || dev == device, "this process already runs nets on device %d; libromp_hip.so serves ONE device per "
+                 "process (launch one process per GPU), current device is %d", device, dev);
+    if (device >= 0) return ROMP_OK;
+    hipDeviceProp_t prop;
+    ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    g_dev.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (!g_dev.queue_scratch) ROMP_HIP_CHECK(hipMalloc((void**)&g_dev.queue_scratch, QUEUE_INTS * sizeof(int)));
+    if (!g_dev.zero) ROMP_HIP_CHECK(hipMalloc((void**)&g_dev.zero, 256));
+    ROMP_HIP_CHECK(hipMemset(g_dev.zero, 0, 256));
+    { const char* e = getenv("ROMP_CONV_TRACE");
+      if (e && atoi(e) && !g_dev.trace) ROMP_HIP_CHECK(hipMalloc((void**)&g_dev.trace, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long))); }
+    int (*const units[])() = {setup_conv_variants, setup_bblock32, setup_bblock32r, setup_bblock64, setup_seam1x1, setup_fuseup, setup_stem2, setup_stem7p};
+    for (auto unit : units) {
+        const int rc = unit();
+        if (rc) return rc;
+    }
+    device = dev;
+    return ROMP_OK;
+}
 
 static bool variant_ok(const ConvVariant& v, const romp_op& op, int Ho, int Wo) {
     if (v.lds > kMaxLds) return false;
-    if ((v.math == 1 || v.math == 2) && (op.weight_aux == nullptr || (op.cin_pad & 15))) return false;
-    if (v.math >= 3 && (op.weight_h2 == nullptr || op.scale_h2 == nullptr || (op.cin_pad & 15))) return false;
-    if (op.in_fmt == ROMP_FMT_H2 && v.math < 3) return false;
-    if (v.math == 10 && !(op.out_fmt == ROMP_FMT_H2 && op.Cout == op.cout_pad && (op.res_buf == ROMP_BUF_NONE || op.res_fmt == ROMP_FMT_H2) &&
+    if ((v.math == MATH_BX3 || v.math == MATH_BXD) && (op.weight_aux == nullptr || (op.cin_pad & 15))) return false;
+    if (v.math >= MATH_H2 && (op.weight_h2 == nullptr || op.scale_h2 == nullptr || (op.cin_pad & 15))) return false;
+    if (op.in_fmt == ROMP_FMT_H2 && v.math < MATH_H2) return false;
+    if (v.math == MATH_H2K && !(op.out_fmt == ROMP_FMT_H2 && op.Cout == op.cout_pad && (op.res_buf == ROMP_BUF_NONE || op.res_fmt == ROMP_FMT_H2) &&
                           op.out_rstride == 0 && op.out_bstride == 0)) return false;      // conv_h2k: the direct H2 epilogue is its only one
-    if (v.math >= 8 && op.in_fmt != ROMP_FMT_H2) return false;                         // register-weight kernels: pixels arrive by LDS-DMA too   // the DMA pipeline copies pre-split pixels
+    if (v.math >= MATH_H2R && op.in_fmt != ROMP_FMT_H2) return false;                         // register-weight kernels: pixels arrive by LDS-DMA too   // the DMA pipeline copies pre-split pixels
     if ((op.out_fmt == ROMP_FMT_H2 || op.res_fmt == ROMP_FMT_H2) && !(op.Cout == op.cout_pad)) return false;   // vector epilogue only
     if (v.ks != op.ksize || v.s != op.stride) return false;
     if (Wo % v.tw) return false;                     // rows may be partial (masked), columns may not
@@ -141,7 +145,7 @@ static int choose_variant(const romp_op& op, int Ho, int Wo, int B) {
     return best;
 }
 
-static void out_dims(const romp_op& op, int* Ho, int* Wo) {
+void conv_out_dims(const romp_op& op, int* Ho, int* Wo) {
     const int kh = op.ksize == 13 ? 1 : op.ksize, kw = op.ksize == 13 ? 3 : op.ksize;
     if (op.ksize == 2) { *Ho = op.H / op.stride; *Wo = op.W / op.stride; return; }   // 2x2: pad_h + (the other side) = 1 in total
     *Ho = (op.H + 2 * (kh / 2) - kh) / op.stride + 1;
@@ -162,13 +166,13 @@ bool conv_variant_tunable(const romp_op& op, int variant) { return conv_variant_
 bool conv_variant_valid(const romp_op& op, int variant) {
     collect_variants();
     int Ho, Wo;
-    out_dims(op, &Ho, &Wo);
+    conv_out_dims(op, &Ho, &Wo);
     return variant >= 0 && variant < kNumVariants && variant_ok(kVariants[variant], op, Ho, Wo);
 }
 
 int launch_conv(const romp_op& op, const float* in, const float* res, float* out, int B, int mode,
-                int variant, int* queue, hipStream_t st, int wg_cap) {
-    { const int rc = ensure_attrs(); if (rc) return rc; }         // one-time setup (zero page, scratch queue, LDS attributes)
+                int variant, int* queue, const LaunchCtx& c) {
+    const hipStream_t st = c.st;
     ROMP_REQUIRE(op.ksize == 1 || op.ksize == 2 || op.ksize == 3 || op.ksize == 13, "conv: ksize %d unsupported", op.ksize);
     ROMP_REQUIRE(op.stride == 1 || op.stride == 2, "conv: stride %d unsupported", op.stride);
     ROMP_REQUIRE(op.groups >= 1, "conv: groups must be >= 1");
@@ -179,7 +183,7 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
     p.w3 = reinterpret_cast<const uint4*>(op.weight_aux);
     p.wh = reinterpret_cast<const uint4*>(op.weight_h2);
     p.scale_h = op.scale_h2;
-    p.zero = g_zero;
+    p.zero = g_dev.zero;
     p.act_scale = ldexpf(1.f, op.act_shift);
     p.inv_act_scale = ldexpf(1.f, -op.act_shift);
     p.in_h2 = op.in_fmt == ROMP_FMT_H2; p.out_h2 = op.out_fmt == ROMP_FMT_H2; p.res_h2 = res && op.res_fmt == ROMP_FMT_H2;
@@ -190,7 +194,7 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
         ROMP_REQUIRE(((op.res_cstride | op.res_coff | op.res_gstride) & 7) == 0 || !p.res_h2, "conv: H2 residual needs octet-aligned channels");
     }
     p.H = op.H; p.W = op.W;
-    out_dims(op, &p.Ho, &p.Wo);
+    conv_out_dims(op, &p.Ho, &p.Wo);
     p.Cout = op.Cout; p.cin_valid = op.Cin; p.cin_pad = op.cin_pad; p.cout_pad = op.cout_pad;
     p.in_cs = op.in_cstride; p.in_co = op.in_coff; p.in_gs = op.in_gstride;
     p.out_cs = op.out_cstride; p.out_co = op.out_coff; p.out_gs = op.out_gstride;
@@ -198,7 +202,7 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
     p.relu = op.relu;
     p.relu_from = op.relu ? op.relu_from : 0;
     ROMP_REQUIRE(p.relu_from >= 0 && (p.relu_from & 31) == 0, "conv: relu_from %d must be a multiple of 32", op.relu_from);
-    p.sat = g_sat;
+    p.sat = c.sat;
     p.w_gs = (op.ksize == 13 ? 3 : op.ksize * op.ksize) * op.cin_pad * op.cout_pad;
     const int kh = op.ksize == 13 ? 1 : op.ksize, kw = op.ksize == 13 ? 3 : op.ksize;
     p.pad_h = op.pad_h >= 0 ? op.pad_h : kh / 2;
@@ -233,18 +237,18 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
     p.n_queues = (p.tiles_total % 8 == 0) ? 8 : 1;
     p.per_queue = (p.tiles_total / p.n_queues) * p.ns_total;
     if (queue == nullptr) {
-        queue = g_queue_scratch;
+        queue = g_dev.queue_scratch;
         ROMP_HIP_CHECK(hipMemsetAsync(queue, 0, QUEUE_INTS * sizeof(int), st));
     }
     p.queue = queue;
     const long items = (long)p.tiles_total * p.ns_total;
-    long grid = (long)g_num_cu * ((wg_cap > 0 && wg_cap < v.occ) ? wg_cap : v.occ);   // wg_cap: leave room for a co-resident kernel
+    long grid = (long)g_dev.num_cu * ((c.wg_cap > 0 && c.wg_cap < v.occ) ? c.wg_cap : v.occ);   // wg_cap: leave room for a co-resident kernel
     const long want = v.pp ? (items + 1) / 2 : items;         // a ping-pong workgroup runs two item streams
     if (grid > want) grid = want;
     if (p.n_queues == 8) grid = grid >= 8 ? (grid / 8) * 8 : 8;    // same number of workgroups per queue
-    if (g_trace) {
-        p.trace = g_trace;
-        ROMP_HIP_CHECK(hipMemsetAsync(g_trace, 0, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long), st));
+    if (g_dev.trace) {
+        p.trace = g_dev.trace;
+        ROMP_HIP_CHECK(hipMemsetAsync(g_dev.trace, 0, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long), st));
     }
     hipLaunchKernelGGL(v.fn, dim3((unsigned)grid), dim3(v.threads ? v.threads : (v.pp ? 512 : 256)), v.lds, st, p);
     ROMP_HIP_CHECK(hipGetLastError());
@@ -253,37 +257,42 @@ int launch_conv(const romp_op& op, const float* in, const float* res, float* out
 
 // the (zeroed) stamp buffer for a kernel launched outside launch_conv (the fused BasicBlock), or nullptr when tracing is off
 unsigned long long* conv_trace_arm(hipStream_t st) {
-    {   // never allocate or memset inside a stream capture (the fused kernels call this from their launch path): tracing is a
-        // debugging aid for eager launches (romp_net_profile, romp_conv_forward)
+    if (!g_dev.trace) return nullptr;
+    {   // never memset inside a stream capture (the fused kernels call this from their launch path): tracing is a debugging aid for
+        // eager launches (romp_net_profile, romp_conv_forward)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return nullptr;
     }
-    if (!g_trace) {
-        const char* e = getenv("ROMP_CONV_TRACE");
-        if (!(e && atoi(e))) return nullptr;
-        if (hipMalloc((void**)&g_trace, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-    }
-    if (hipMemsetAsync(g_trace, 0, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long), st) != hipSuccess) return nullptr;
-    return g_trace;
+    if (hipMemsetAsync(g_dev.trace, 0, (size_t)TRACE_WAVES * TRACE_SLOTS * sizeof(unsigned long long), st) != hipSuccess) return nullptr;
+    return g_dev.trace;
 }
 
 int conv_trace_read(unsigned long long* dst_host, int max_words) {
-    ROMP_REQUIRE(g_trace != nullptr, "conv trace is off (set ROMP_CONV_TRACE=1 before the first launch)");
+    ROMP_REQUIRE(g_dev.trace != nullptr, "conv trace is off (set ROMP_CONV_TRACE=1 before the first launch)");
     const int n = max_words < TRACE_WAVES * TRACE_SLOTS ? max_words : TRACE_WAVES * TRACE_SLOTS;
     ROMP_HIP_CHECK(hipDeviceSynchronize());
-    ROMP_HIP_CHECK(hipMemcpy(dst_host, g_trace, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    ROMP_HIP_CHECK(hipMemcpy(dst_host, g_dev.trace, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return n;
 }
+
+// family -> the name tune tables and profiles/ key on; `alt`: its ping-pong (f32) / four-workgroups-per-CU (f16x2) build
+static const struct { ConvMath math; const char* name; const char* alt; } kFamilies[] = {
+    {MATH_F32, "conv_mfma", "conv_pp"}, {MATH_BX3, "conv_bx3", "conv_bx3"}, {MATH_BXD, "conv_bxd", "conv_bxd"},
+    {MATH_H2, "conv_h2", "conv_h2o"},   {MATH_H2D, "conv_h2d", "conv_h2do"}, {MATH_H2R, "conv_h2r", "conv_h2r"},
+    {MATH_H2S, "conv_h2s", "conv_h2s"}, {MATH_H2K, "conv_h2k", "conv_h2k"},  {MATH_H2G, "conv_h2g", "conv_h2g"},
+};
 
 int describe_conv(const romp_op& op, int B, int variant, char* out, int n) {
     collect_variants();
     int Ho, Wo;
-    out_dims(op, &Ho, &Wo);
+    conv_out_dims(op, &Ho, &Wo);
     if (variant < 0) variant = choose_variant(op, Ho, Wo, B);
     ROMP_REQUIRE(variant >= 0 && variant < kNumVariants, "describe: no variant");
     const ConvVariant& v = kVariants[variant];
-    snprintf(out, n, "%s_k%ds%d_mt%d_nt%d_tw%d_ck%d", v.math == 11 ? "conv_h2g" : v.math == 10 ? "conv_h2k" : v.math == 9 ? "conv_h2s" : v.math == 8 ? "conv_h2r" : v.math == 4 ? (v.o4 ? "conv_h2do" : "conv_h2d") : v.math == 3 ? (v.o4 ? "conv_h2o" : "conv_h2") : v.math == 2 ? "conv_bxd" : v.math ? "conv_bx3" : (v.pp ? "conv_pp" : "conv_mfma"), v.ks, v.s, v.mt, v.nt,
-             v.tw, v.ck);
+    const char* name = "conv";
+    for (const auto& f : kFamilies)
+        if (f.math == v.math) name = (v.pp || v.o4) ? f.alt : f.name;
+    snprintf(out, n, "%s_k%ds%d_mt%d_nt%d_tw%d_ck%d", name, v.ks, v.s, v.mt, v.nt, v.tw, v.ck);
     return ROMP_OK;
 }
 

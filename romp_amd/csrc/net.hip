@@ -45,7 +45,6 @@ struct romp_net {
     std::vector<float*> bufs;
     int* queues = nullptr;               // 2 lanes x n_ops x QUEUE_INTS work counters, zeroed at the start of a forward
     int* sat = nullptr;                  // saturation counter (conv_common.h sat_report): cumulative since create / the last reset
-    bool sat_checked = false;            // also launch the counting builds of the fused-block kernels (env ROMP_CHECK_FINITE=1, range scan)
     int max_batch = 0;
     int mode = 0;
     int use_graph = 0;
@@ -92,9 +91,38 @@ static float* resolve_out(romp_net* n, int buf, float* center, float* params, in
     return nullptr;
 }
 
+// Per op kind: its name (romp_conv_describe: profiles key on it) and whether it is a MARKER, an op that launches nothing -- NOP holds
+// the fields of a layer the next op runs fused, the others are stream topology that run_lane / build_graph interpret.
+struct KindInfo { const char* name; bool marker; };
+static const KindInfo* kind_info(int kind) {
+    static const KindInfo kKinds[] = {
+        {nullptr, false},
+        /* ROMP_OP_STEM 1 */ {"stem_conv", false}, /* CONV 2 */ {"conv", false},           /* FUSESUM 3 */ {"fusesum", false},
+        /* FORK 4 */ {"fork", true},               /* JOIN 5 */ {"join", true},            /* BEV_PACK 6 */ {"bev_pack", false},
+        /* BEV_MAPS 7 */ {"bev_maps", false},      /* CONV3D 8 */ {"conv3d", false},       /* STEM7 9 */ {"stem7_conv", false},
+        /* MAXPOOL 10 */ {"maxpool3s2", false},    /* KSUM 11 */ {"ksum", false},          /* NOP 12 */ {"nop", true},
+        /* BBLOCK32 13 */ {"bblock32", false},     /* BBLOCK64 14 */ {"bblock64", false},  /* SEAM1X1 15 */ {"seam1x1", false},
+        /* FUSEUP 16 */ {"fuseup", false},         /* RECORD 17 */ {"record", true},       /* WAIT 18 */ {"wait", true},
+        /* STEM2 19 */ {"stem2", false},           /* STEM7P 20 */ {"stem7p", false},
+    };
+    static_assert(sizeof(kKinds) / sizeof(kKinds[0]) == ROMP_OP_STEM7P + 1, "one row per op kind");
+    return kind > 0 && kind <= ROMP_OP_STEM7P ? &kKinds[kind] : nullptr;
+}
+static bool is_marker(const romp_op& op) { const KindInfo* k = kind_info(op.kind); return k && k->marker; }
+
+static bool lanes_active(const romp_net* n, int B) { return n->split == 2 && n->mode == 0 && B >= 2 && !(B & 1); }
+
+// What the launches of a forward of B images are told.  The cap: a two-lane net's forward that does not split (odd / single-image
+// batch, naive mode) takes the whole chip.
+static LaunchCtx forward_ctx(const romp_net* n, int B, hipStream_t st) {
+    return LaunchCtx{st, n->sat, (n->split == 2 && !lanes_active(n, B)) ? 0 : n->wg_cap};
+}
+static LaunchCtx on_stream(LaunchCtx c, hipStream_t st) { c.st = st; return c; }
+
 static int run_op(romp_net* n, size_t idx, int variant, const float* image, int B, float* center, float* params,
-                  hipStream_t st, int lane = 0, int b0 = 0) {
+                  const LaunchCtx& c, int lane = 0, int b0 = 0) {
     const romp_op& op = n->ops[idx];
+    if (is_marker(op)) return ROMP_OK;       // stream markers: handled by run_lane / build_graph; NOP: fused into the next op
     int* queue = n->queues + ((size_t)lane * n->ops.size() + idx) * QUEUE_INTS;
     auto resolve_in = [&](romp_net* nn, int buf, const float* img) { return ::resolve_in(nn, buf, img, b0); };
     auto resolve_out = [&](romp_net* nn, int buf, float* c, float* p) { return ::resolve_out(nn, buf, c, p, b0); };
@@ -103,31 +131,31 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
             const float* in = resolve_in(n, op.in_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(in && out, "stem: bad buffers %d -> %d", op.in_buf, op.out_buf);
-            return launch_stem(op, in, out, B, st);
+            return launch_stem(op, in, out, B, c);
         }
         case ROMP_OP_STEM7: {
             const float* in = resolve_in(n, op.in_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(in && out, "stem7: bad buffers %d -> %d", op.in_buf, op.out_buf);
-            return launch_stem7(op, in, out, B, st);
+            return launch_stem7(op, in, out, B, c);
         }
         case ROMP_OP_STEM7P: {
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(image && out && op.in_buf == ROMP_BUF_IMAGE, "stem7p: bad buffers");
-            return launch_stem7p(op, image, out, B, st);
+            return launch_stem7p(op, image, out, B, c);
         }
         case ROMP_OP_MAXPOOL: {
             const float* in = resolve_in(n, op.in_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(in && out, "maxpool: bad buffers %d -> %d", op.in_buf, op.out_buf);
-            return launch_maxpool(op, in, out, B, st);
+            return launch_maxpool(op, in, out, B, c);
         }
         case ROMP_OP_BEV_PACK: {
             const float* fv = resolve_in(n, op.in_buf, image);
             const float* ft = resolve_in(n, op.res_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(fv && ft && out, "bev_pack: bad buffers");
-            return launch_bev_pack(fv, op.in_cstride, ft, op.res_cstride, out, B, st);
+            return launch_bev_pack(fv, op.in_cstride, ft, op.res_cstride, out, B, c);
         }
         case ROMP_OP_BEV_MAPS: {
             const float* fv = resolve_in(n, op.in_buf, image);
@@ -135,14 +163,14 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
             float* c3 = resolve_out(n, op.out_buf, center, params);
             float* cam = resolve_out(n, op.term_buf[0], center, params);
             ROMP_REQUIRE(fv && bv && c3 && cam && op.weight, "bev_maps: bad buffers");
-            return launch_bev_maps(fv, op.in_cstride, bv, op.res_cstride, op.weight, c3, cam, B, st);
+            return launch_bev_maps(fv, op.in_cstride, bv, op.res_cstride, op.weight, c3, cam, B, c);
         }
         case ROMP_OP_CONV3D: {
             const float* in = resolve_in(n, op.in_buf, image);
             const float* res = op.res_buf == ROMP_BUF_NONE ? nullptr : resolve_in(n, op.res_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(in && out && op.weight && op.scale && op.shift, "conv3d: bad buffers");
-            return launch_conv3d(op.Cin, op.weight, op.scale, op.shift, op.relu, in, res, out, B, st);
+            return launch_conv3d(op.Cin, op.weight, op.scale, op.shift, op.relu, in, res, out, B, c);
         }
         case ROMP_OP_CONV: {
             if (op.ksize == 13) {
@@ -152,14 +180,14 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
                 ROMP_REQUIRE(in1 && out1 && op.res_buf == ROMP_BUF_NONE, "conv1d: bad buffers");
                 romp_op o1 = op;
                 o1.H = B;
-                return launch_conv(o1, in1, nullptr, out1, 1, n->mode, variant, queue, st, n->wg_cap);
+                return launch_conv(o1, in1, nullptr, out1, 1, n->mode, variant, queue, c);
             }
             const float* in = resolve_in(n, op.in_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             const float* res = op.res_buf == ROMP_BUF_NONE ? nullptr : resolve_in(n, op.res_buf, image);
             ROMP_REQUIRE(in && out, "conv: bad buffers %d -> %d", op.in_buf, op.out_buf);
             ROMP_REQUIRE(op.res_buf == ROMP_BUF_NONE || res, "conv: bad residual buffer %d", op.res_buf);
-            return launch_conv(op, in, res, out, B, n->mode, variant, queue, st, n->wg_cap);
+            return launch_conv(op, in, res, out, B, n->mode, variant, queue, c);
         }
         case ROMP_OP_FUSESUM: {
             FuseTerm t[4];
@@ -175,7 +203,7 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
             }
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(out, "fusesum: bad out buffer %d", op.out_buf);
-            return launch_fusesum(t, op.n_terms, out, B, op.H, op.W, op.Cout, op.out_cstride, op.out_coff, op.relu, st, op.out_fmt, op.act_shift);
+            return launch_fusesum(t, op.n_terms, out, B, op.H, op.W, op.Cout, op.out_cstride, op.out_coff, op.relu, c, op.out_fmt, op.act_shift);
         }
         case ROMP_OP_FUSEUP: {
             FuseTerm t[4];
@@ -188,34 +216,34 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
             }
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(out, "fuseup: bad out buffer %d", op.out_buf);
-            return launch_fuseup(op, t, out, B, st);
+            return launch_fuseup(op, t, out, B, c);
         }
         case ROMP_OP_KSUM: {
             const float* part = resolve_in(n, op.in_buf, image);
             const float* res = op.res_buf == ROMP_BUF_NONE ? nullptr : resolve_in(n, op.res_buf, image);
             float* out = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(part && out && (op.res_buf == ROMP_BUF_NONE || res), "ksum: bad buffers %d -> %d", op.in_buf, op.out_buf);
-            return launch_ksum(op, part, res, out, B, st);
+            return launch_ksum(op, part, res, out, B, c);
         }
         case ROMP_OP_BBLOCK32: {
             ROMP_REQUIRE(idx > 0 && n->ops[idx - 1].kind == ROMP_OP_NOP, "bblock32: the op before it must be the NOP holding the first conv");
             const float* x = resolve_in(n, op.res_buf, image);
             float* y = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(x && y && n->ops[idx - 1].in_buf == op.res_buf, "bblock32: bad buffers %d -> %d", op.res_buf, op.out_buf);
-            return launch_bblock32(n->ops[idx - 1], op, x, y, B, queue, st);
+            return launch_bblock32(n->ops[idx - 1], op, x, y, B, queue, c);
         }
         case ROMP_OP_BBLOCK64: {
             ROMP_REQUIRE(idx > 0 && n->ops[idx - 1].kind == ROMP_OP_NOP, "bblock64: the op before it must be the NOP holding the first conv");
             const float* x = resolve_in(n, op.res_buf, image);
             float* y = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(x && y && n->ops[idx - 1].in_buf == op.res_buf, "bblock64: bad buffers %d -> %d", op.res_buf, op.out_buf);
-            return launch_bblock64(n->ops[idx - 1], op, x, y, B, queue, st);
+            return launch_bblock64(n->ops[idx - 1], op, x, y, B, queue, c);
         }
         case ROMP_OP_STEM2: {
             ROMP_REQUIRE(idx > 0 && n->ops[idx - 1].kind == ROMP_OP_NOP && n->ops[idx - 1].in_buf == ROMP_BUF_IMAGE, "stem2: the op before it must be the NOP holding the stem");
             float* y = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(image && y, "stem2: bad buffers");
-            return launch_stem2(n->ops[idx - 1], op, image, y, B, st);
+            return launch_stem2(n->ops[idx - 1], op, image, y, B, c);
         }
         case ROMP_OP_SEAM1X1: {
             ROMP_REQUIRE(idx > 0 && n->ops[idx - 1].kind == ROMP_OP_NOP, "seam1x1: the op before it must be the NOP holding the first conv");
@@ -229,14 +257,8 @@ static int run_op(romp_net* n, size_t idx, int variant, const float* image, int 
             float* t = resolve_out(n, a.out_buf, center, params);
             float* u = resolve_out(n, op.out_buf, center, params);
             ROMP_REQUIRE(m && x && t && u && op.in_buf == a.out_buf, "seam1x1: bad buffers");
-            return launch_seam1x1(a, op, d, m, x, t, u, B, st);
+            return launch_seam1x1(a, op, d, m, x, t, u, B, c);
         }
-        case ROMP_OP_NOP:
-        case ROMP_OP_FORK:
-        case ROMP_OP_JOIN:
-        case ROMP_OP_RECORD:
-        case ROMP_OP_WAIT:
-            return ROMP_OK;              // stream markers: handled by run_all; NOP: fused into the next op
         default:
             set_error("unknown op kind %d", op.kind);
             return ROMP_EINVAL;
@@ -264,8 +286,9 @@ static int reset_queues(romp_net* n, hipStream_t st) {
 }
 
 // One op sequence (a whole batch, or one batch lane) on `st` with its FORK/JOIN regions on the lane's side streams.
-static int run_lane(romp_net* n, const float* image, int B, float* center, float* params, hipStream_t st, int lane, int b0,
+static int run_lane(romp_net* n, const float* image, int B, float* center, float* params, const LaunchCtx& c, int lane, int b0,
                     hipEvent_t ev_after_first_convs, size_t first_op = 0) {
+    const hipStream_t st = c.st;
     const std::vector<int>* tv = tuned_for(n, B);
     const bool ms = n->use_streams && n->mode == 0;
     int convs_seen = 0;
@@ -294,7 +317,7 @@ static int run_lane(romp_net* n, const float* image, int B, float* center, float
             else ROMP_HIP_CHECK(hipStreamWaitEvent(s, n->ev_edge[lane][op.Cin], 0));
             continue;
         }
-        const int rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, s, lane, b0);
+        const int rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, on_stream(c, s), lane, b0);
         if (rc) return rc;
         if (ev_after_first_convs && op.kind == ROMP_OP_CONV && ++convs_seen == 2)      // lane 1 starts ~two layers behind lane 0
             ROMP_HIP_CHECK(hipEventRecord(ev_after_first_convs, st));
@@ -308,9 +331,10 @@ static int run_lane(romp_net* n, const float* image, int B, float* center, float
 // hipStreamEndCapture walks those lists recursively -- off the end of the stack (ROCm 7.0 / 7.2; backtrace in profiles/r04_notes.md).
 // So: every op is captured ALONE on a scratch stream (a one-stream capture: a chain of kernel / memset nodes), its nodes are re-added
 // to the forward's graph, and the dependencies come from the program: stream order, FORK / JOIN, RECORD / WAIT.  `whole`: a whole
-// forward (queue reset in front, as run_all) -- otherwise one batch lane (as run_lane; the caller resets the queues).
+// forward (queue reset in front, as run_all) -- otherwise one batch lane (as run_lane; the caller resets the queues).  `c`: the
+// forward's launch context (its stream is not used: the scratch stream takes its place).
 static int build_graph(romp_net* n, const float* image, int B, float* center, float* params, int lane, int b0, size_t first_op, bool whole,
-                       hipGraph_t* out) {
+                       const LaunchCtx& c, hipGraph_t* out) {
     typedef std::vector<hipGraphNode_t> Nodes;
     struct Owned {                                             // a graph that dies with its scope unless released
         hipGraph_t g = nullptr;
@@ -368,17 +392,17 @@ static int build_graph(romp_net* n, const float* image, int B, float* center, fl
         }
         return ROMP_OK;
     };
-    conv_set_sat_counter(n->sat, n->sat_checked);
-    const int cap = n->wg_cap;
-    if (whole && n->split == 2) n->wg_cap = 0;                 // an unsplit forward takes the whole chip (run_all)
-    conv_set_wg_cap(n->wg_cap);
     int rc = whole ? add_op(0, [&](hipStream_t s) { return reset_queues(n, s); }) : ROMP_OK;
     const std::vector<int>* tv = tuned_for(n, B);
     const bool ms = n->use_streams && n->mode == 0;
     for (size_t i = first_op; i < n->ops.size() && !rc; ++i) {
         const romp_op& op = n->ops[i];
         const int s = (ms && op.stream >= 1 && op.stream <= 3) ? op.stream : 0;
-        switch (op.kind) {
+        if (!is_marker(op)) {
+            rc = add_op(s, [&](hipStream_t st) { return run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, on_stream(c, st), lane, b0); });
+            continue;
+        }
+        switch (op.kind) {                                     // (NOP: nothing)
             case ROMP_OP_FORK:
                 for (int k = 1; ms && k <= op.Cin && k <= 3; ++k) merge(frontier[k], frontier[0]);
                 break;
@@ -391,46 +415,49 @@ static int build_graph(romp_net* n, const float* image, int B, float* center, fl
             case ROMP_OP_WAIT:
                 if (ms) merge(frontier[s], events[op.Cin]);
                 break;
-            case ROMP_OP_NOP:
-                break;
-            default:
-                rc = add_op(s, [&](hipStream_t st) { return run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, st, lane, b0); });
         }
     }
-    n->wg_cap = cap;
     if (rc) return rc;
     *out = top.g;
     top.g = nullptr;
     return ROMP_OK;
 }
 
-static bool lanes_active(const romp_net* n, int B) { return n->split == 2 && n->mode == 0 && B >= 2 && !(B & 1); }
-
 static int run_all(romp_net* n, const float* image, int B, float* center, float* params, hipStream_t st, size_t first_op = 0) {
-    conv_set_sat_counter(n->sat, n->sat_checked);
-    conv_set_wg_cap(n->wg_cap);
+    const LaunchCtx c = forward_ctx(n, B, st);
     int rc = reset_queues(n, st);
     if (rc) return rc;
-    if (!lanes_active(n, B)) {
-        const int cap = n->wg_cap;
-        if (n->split == 2) n->wg_cap = 0;              // an unsplit forward (odd / single-image batch) takes the whole chip
-        rc = run_lane(n, image, B, center, params, st, 0, 0, nullptr, first_op);
-        n->wg_cap = cap;
-        return rc;
-    }
+    if (!lanes_active(n, B)) return run_lane(n, image, B, center, params, c, 0, 0, nullptr, first_op);
     const int B0 = B / 2;
     ROMP_HIP_CHECK(hipEventRecord(n->ev_begin, st));                        // after the queue reset
     ROMP_HIP_CHECK(hipEventRecord(n->ev_offset, st));                       // (re-recorded two convs into lane 0)
-    rc = run_lane(n, image, B0, center, params, st, 0, 0, n->ev_offset);
+    rc = run_lane(n, image, B0, center, params, c, 0, 0, n->ev_offset);
     if (rc) return rc;
     ROMP_HIP_CHECK(hipStreamWaitEvent(n->lane_main, n->ev_begin, 0));
     ROMP_HIP_CHECK(hipStreamWaitEvent(n->lane_main, n->ev_offset, 0));
     rc = run_lane(n, image + (size_t)B0 * n->image_floats, B0, center + (size_t)B0 * n->center_floats,
-                  params + (size_t)B0 * n->params_floats, n->lane_main, 1, B0, nullptr);
+                  params + (size_t)B0 * n->params_floats, on_stream(c, n->lane_main), 1, B0, nullptr);
     if (rc) return rc;
     ROMP_HIP_CHECK(hipEventRecord(n->ev_done, n->lane_main));
     ROMP_HIP_CHECK(hipStreamWaitEvent(st, n->ev_done, 0));
     return ROMP_OK;
+}
+
+// What a fused op's launcher requires of the ops alone: checked for every such op when the net is created.  (That the ops in front
+// of it are the NOPs it reads is run_op's to say; an op too early in the program for them is reported there.)
+static int check_fused_op(const romp_op* ops, int i) {
+    const romp_op& op = ops[i];
+    switch (op.kind) {
+        case ROMP_OP_BBLOCK32: return i > 0 ? check_bblock32(ops[i - 1], op) : ROMP_OK;
+        case ROMP_OP_BBLOCK64: return i > 0 ? check_bblock64(ops[i - 1], op) : ROMP_OK;
+        case ROMP_OP_SEAM1X1:
+            if (i == 0 || ((op.flags & ROMP_OPF_SEAM_DS) && i < 2)) return ROMP_OK;
+            return check_seam1x1(ops[i - 1], op, (op.flags & ROMP_OPF_SEAM_DS) ? &ops[i - 2] : nullptr);
+        case ROMP_OP_STEM2: return i > 0 ? check_stem2(ops[i - 1], op) : ROMP_OK;
+        case ROMP_OP_STEM7P: return check_stem7p(op);
+        case ROMP_OP_FUSEUP: return check_fuseup(op);
+        default: return ROMP_OK;
+    }
 }
 
 extern "C" {
@@ -441,52 +468,10 @@ const char* romp_last_error(void) { return romp::g_err; }
 int romp_net_create(romp_net** out, const romp_op* ops_host, int n_ops, const int64_t* buf_floats, int n_bufs,
                     int max_batch) {
     ROMP_REQUIRE(out && ops_host && n_ops > 0 && n_bufs >= 0 && max_batch > 0, "romp_net_create: bad arguments");
-    {   // One device per process (the design: one process per GPU, torch.distributed over RCCL): the launchers cache their one-time
-        // set-up -- raised dynamic-LDS limits, CU count, zero pages, occupancy -- per PROCESS.  A second net on another device would
-        // silently run with the first device's, so it is refused here.
-        static int g_device = -1;
-        int dev = -1;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        if (g_device < 0) g_device = dev;
-        ROMP_REQUIRE(dev == g_device, "romp_net_create: this process already runs nets on device %d; libromp_hip.so serves ONE device per "
-                     "process (launch one process per GPU), current device is %d", g_device, dev);
-    }
-    { const int rc = conv_init(); if (rc) return rc; }
-    for (int i = 1; i < n_ops; ++i)
-        if (ops_host[i].kind == ROMP_OP_SEAM1X1) {
-            const int rc = launch_seam1x1(ops_host[i - 1], ops_host[i], nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-            break;
-        }
-    for (int i = 1; i < n_ops; ++i)
-        if (ops_host[i].kind == ROMP_OP_STEM2) {
-            const int rc = launch_stem2(ops_host[i - 1], ops_host[i], nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-            break;
-        }
-    for (int i = 0; i < n_ops; ++i)
-        if (ops_host[i].kind == ROMP_OP_STEM7P) {
-            const int rc = launch_stem7p(ops_host[i], nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-            break;
-        }
-    for (int i = 0; i < n_ops; ++i)                            // (every instantiation in use: cheap, idempotent)
-        if (ops_host[i].kind == ROMP_OP_FUSEUP) {
-            const int rc = launch_fuseup(ops_host[i], nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-    for (int i = 0, seen = 0; i < n_ops && seen != 3; ++i) {  // the fused blocks' one-time set-up (hipMalloc / attributes) must not run inside a stream capture
-        const int kind = ops_host[i].kind;
-        if (kind == ROMP_OP_BBLOCK32 && !(seen & 1) && i > 0) {
-            const int rc = launch_bblock32(ops_host[i - 1], ops_host[i], nullptr, nullptr, 0, nullptr, nullptr);
-            if (rc) return rc;
-            seen |= 1;
-        }
-        if (kind == ROMP_OP_BBLOCK64 && !(seen & 2) && i > 0) {
-            const int rc = launch_bblock64(ops_host[i - 1], ops_host[i], nullptr, nullptr, 0, nullptr, nullptr);
-            if (rc) return rc;
-            seen |= 2;
-        }
+    { const int rc = device_init(); if (rc) return rc; }
+    for (int i = 0; i < n_ops; ++i) {
+        const int rc = check_fused_op(ops_host, i);
+        if (rc) return rc;
     }
     romp_net* n = new romp_net();
     n->ops.assign(ops_host, ops_host + n_ops);
@@ -531,7 +516,6 @@ int romp_net_create(romp_net** out, const romp_op* ops_host, int n_ops, const in
         romp_net_destroy(n);
         return ROMP_ENOMEM;
     }
-    { const char* e = getenv("ROMP_CHECK_FINITE"); n->sat_checked = e && e[0] && strcmp(e, "0") != 0; }
     bool ok = hipStreamCreateWithFlags(&n->lane_main, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&n->scratch, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&n->ev_begin, hipEventDisableTiming) == hipSuccess &&
@@ -601,7 +585,6 @@ int romp_net_forward(romp_net* n, const float* image, int B, float* center, floa
     ROMP_REQUIRE(n && image && center && params && B > 0, "romp_net_forward: bad arguments");
     if (B > n->max_batch) { set_error("batch %d > max_batch %d", B, n->max_batch); return ROMP_ECAPACITY; }
     hipStream_t st = (hipStream_t)stream;
-    conv_set_sat_counter(n->sat, n->sat_checked);
     // Streams off (the profiling configuration: every op on the caller's stream) replays EAGERLY even in graph mode.  A forward
     // without branch streams is a single-chain hipGraph, and ROCm 7.x's packet-capture path for such graphs faults (GPU memory
     // access fault, 3 of 6 runs) when the host calls hipDeviceSynchronize between replays of a short job -- gone with
@@ -619,10 +602,11 @@ int romp_net_forward(romp_net* n, const float* image, int B, float* center, floa
         ROMP_HIP_CHECK(hipStreamSynchronize(n->lane_main));
         drop_graphs(n);
     }
+    const LaunchCtx ctx = forward_ctx(n, B, st);
     auto build = [&](const GraphKey& key, const float* im, int Bl, float* ce, float* pa, int lane, int b0, size_t first_op, bool whole) -> int {
         if (n->graphs.count(key)) return ROMP_OK;
         hipGraph_t g = nullptr;
-        const int rc = build_graph(n, im, Bl, ce, pa, lane, b0, first_op, whole, &g);
+        const int rc = build_graph(n, im, Bl, ce, pa, lane, b0, first_op, whole, ctx, &g);
         if (rc) return rc;
         hipGraphExec_t ge = nullptr;
         const hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
@@ -634,7 +618,7 @@ int romp_net_forward(romp_net* n, const float* image, int B, float* center, floa
     if (!lanes_active(n, B)) {
         const GraphKey key{B, key_image, center, params, -1};
         if (stem_out) {
-            const int rc0 = run_op(n, n->eager_ops - 1, -1, image, B, center, params, st);     // (the ops in front of it in the prefix are NOPs)
+            const int rc0 = run_op(n, n->eager_ops - 1, -1, image, B, center, params, ctx);     // (the ops in front of it in the prefix are NOPs)
             if (rc0) return rc0;
         }
         const int rc = build(key, image, B, center, params, 0, 0, stem_out ? n->eager_ops : 0, true);
@@ -669,16 +653,15 @@ int romp_net_autotune(romp_net* n, int B, int iters, void* stream) {
     ROMP_REQUIRE(n && B > 0 && iters > 0, "romp_net_autotune: bad arguments");
     if (B > n->max_batch) { set_error("batch %d > max_batch %d", B, n->max_batch); return ROMP_ECAPACITY; }
     hipStream_t st = (hipStream_t)stream;
-    conv_set_sat_counter(nullptr, false);             // timing runs on whatever the arena holds: nothing to report
+    const LaunchCtx ctx{st, nullptr, n->wg_cap};      // timing runs on whatever the arena holds: nothing to report
     std::vector<int> best(n->ops.size(), -1);
     // Scratch target for ops that read the caller's image or write the caller's output tensors: sized from the program
     // (largest per-image extent any conv touches through a pseudo buffer), not from one model's head.
     size_t scratch_floats = 16;
     for (const romp_op& op : n->ops) {
         if (op.kind != ROMP_OP_CONV) continue;
-        const int kh = op.ksize == 13 ? 1 : op.ksize, kw = op.ksize == 13 ? 3 : op.ksize;
-        const int Ho = op.ksize == 2 ? op.H / op.stride : (op.H + 2 * (kh / 2) - kh) / op.stride + 1;
-        const int Wo = op.ksize == 2 ? op.W / op.stride : (op.W + 2 * (kw / 2) - kw) / op.stride + 1;
+        int Ho, Wo;
+        conv_out_dims(op, &Ho, &Wo);
         if (op.in_buf == ROMP_BUF_IMAGE) scratch_floats = std::max(scratch_floats, (size_t)op.H * op.W * op.in_cstride);
         if (op.res_buf == ROMP_BUF_IMAGE) scratch_floats = std::max(scratch_floats, (size_t)Ho * Wo * op.res_cstride);
         if (op.out_buf == ROMP_BUF_CENTER || op.out_buf == ROMP_BUF_PARAMS)
@@ -718,7 +701,7 @@ int romp_net_autotune(romp_net* n, int B, int iters, void* stream) {
                 rc = reset_queues(n, st);
                 if (rc) break;
                 hipEventRecord(e0, st);
-                rc = run_op(n, i, v, scratch, B, scratch, scratch, st);
+                rc = run_op(n, i, v, scratch, B, scratch, scratch, ctx);
                 hipEventRecord(e1, st);
                 if (hipEventSynchronize(e1) != hipSuccess) { set_error("autotune: kernel failed (op %zu variant %d)", i, v); rc = ROMP_EHIP; break; }
                 float ms = 0.f;
@@ -741,7 +724,7 @@ int romp_net_profile(romp_net* n, const float* image, int B, float* center, floa
     ROMP_REQUIRE(n && image && center && params && ms_out && B > 0 && iters > 0, "romp_net_profile: bad arguments");
     if (B > n->max_batch) { set_error("batch %d > max_batch %d", B, n->max_batch); return ROMP_ECAPACITY; }
     hipStream_t st = (hipStream_t)stream;
-    conv_set_sat_counter(n->sat, n->sat_checked);
+    const LaunchCtx ctx = forward_ctx(n, B, st);
     const size_t nops = n->ops.size();
     std::vector<hipEvent_t> ev(nops + 1);
     for (auto& e : ev) ROMP_HIP_CHECK(hipEventCreate(&e));
@@ -753,7 +736,7 @@ int romp_net_profile(romp_net* n, const float* image, int B, float* center, floa
         if (rc) break;
         hipEventRecord(ev[0], st);
         for (size_t i = 0; i < nops; ++i) {
-            rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, st);
+            rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, ctx);
             if (rc) break;
             hipEventRecord(ev[i + 1], st);
         }
@@ -781,6 +764,7 @@ int romp_net_profile(romp_net* n, const float* image, int B, float* center, floa
 // bytes: eight high then eight low fp16 pieces).  One atomicMax on the float's bit pattern per wave.  (Round 3 reduced over the
 // whole arena buffer: stale data of earlier live ranges and neighbouring channel slices made the figure an upper bound that could
 // mask the too-small-for-fp16 test -- ADVICE r3.)
+namespace romp {
 struct ScanRegion { const float* x; int B; long long bstride; long long npix; int cs, coff, C, h2; float inv_scale; };
 __global__ void range_scan_kernel(ScanRegion r, unsigned* out_max, unsigned* out_bad) {
     float m = 0.f;
@@ -817,6 +801,8 @@ __global__ void range_scan_kernel(ScanRegion r, unsigned* out_max, unsigned* out
     }
 }
 
+}  // namespace romp
+
 // the region an op writes into arena buffer op.out_buf: false for ops whose output is not a dense (pixels x channel slice) block
 // (sparse parity outputs of a transposed conv, the BEV head's 3-D tensors): those are scanned as whole buffers
 static bool op_out_region(const romp_op& op, long long* npix, int* cs, int* coff, int* C) {
@@ -824,9 +810,7 @@ static bool op_out_region(const romp_op& op, long long* npix, int* cs, int* coff
     switch (op.kind) {
         case ROMP_OP_CONV: {
             if (op.ksize == 13 || op.out_rstride > 0 || op.out_bstride > 0) return false;
-            const int k = op.ksize;
-            if (k == 2) { Ho = op.H / op.stride; Wo = op.W / op.stride; }
-            else { Ho = (op.H + 2 * (k / 2) - k) / op.stride + 1; Wo = (op.W + 2 * (k / 2) - k) / op.stride + 1; }
+            conv_out_dims(op, &Ho, &Wo);
             *C = op.groups > 1 ? (op.groups - 1) * op.out_gstride + op.Cout : op.Cout;
             break; }
         case ROMP_OP_STEM: case ROMP_OP_STEM7: Ho = op.H / 2; Wo = op.W / 2; *C = op.Cout; break;
@@ -841,8 +825,8 @@ static bool op_out_region(const romp_op& op, long long* npix, int* cs, int* coff
 
 // Runs the program op by op (one stream, the variants of romp_net_autotune if it ran) and reports for every op that writes an
 // arena buffer the max |x| / non-finite count of the region it wrote (B images) right after the op, and how many saturation events
-// (conv_common.h sat_report: waves that clamped a value at +-65504 while splitting it into fp16 pieces) the op's kernels reported --
-// the fused-block kernels run their counting builds here.  plan.assign_formats uses max |x| (of a float32 lowering) to keep tensors
+// (conv_common.h sat_report: waves that clamped a value at +-65504 while splitting it into fp16 pieces) the op's kernels reported.
+// plan.assign_formats uses max |x| (of a float32 lowering) to keep tensors
 // whose range does not fit the fp16 pieces of the H2 format in float32 and their consumers on the f32 / bf16x3 kernels; on the real
 // program the saturation column says which op clamped (RompNet.range_scan).
 int romp_net_range_scan(romp_net* n, const float* image, int B, float* center, float* params, void* stream,
@@ -861,14 +845,13 @@ int romp_net_range_scan(romp_net* n, const float* image, int B, float* center, f
     }
     // the kernels the FORWARD of this batch runs: with two lanes active every kernel sees B / 2 images and the table measured for that
     const std::vector<int>* tv = tuned_for(n, lanes_active(n, B) ? B / 2 : B);
-    conv_set_sat_counter(n->sat, true);
+    const LaunchCtx ctx = forward_ctx(n, B, st);
     if (rc == ROMP_OK) rc = reset_queues(n, st);
     for (size_t i = 0; i < nops && rc == ROMP_OK; ++i) {
-        rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, st);
+        rc = run_op(n, i, tv ? (*tv)[i] : -1, image, B, center, params, ctx);
         const romp_op& op = n->ops[i];
         if (rc == ROMP_OK && hipMemcpyAsync(d + 2 * nops + i, n->sat, sizeof(int), hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); rc = ROMP_EHIP; }
-        if (rc || op.out_buf < 0 || op.out_buf >= (int)n->bufs.size() || op.kind == ROMP_OP_FORK || op.kind == ROMP_OP_JOIN || op.kind == ROMP_OP_NOP ||
-            op.kind == ROMP_OP_RECORD || op.kind == ROMP_OP_WAIT) continue;
+        if (rc || op.out_buf < 0 || op.out_buf >= (int)n->bufs.size() || is_marker(op)) continue;
         ScanRegion r;
         r.x = n->bufs[op.out_buf]; r.B = B; r.bstride = n->buf_floats[op.out_buf];
         r.h2 = op.out_fmt == ROMP_FMT_H2; r.inv_scale = ldexpf(1.f, -op.act_shift);
@@ -878,7 +861,6 @@ int romp_net_range_scan(romp_net* n, const float* image, int B, float* center, f
         hipLaunchKernelGGL(range_scan_kernel, dim3(1024), dim3(256), 0, st, r, d + i, d + nops + i);
         if (hipGetLastError() != hipSuccess) { set_error("range_scan_kernel launch failed"); rc = ROMP_EHIP; }
     }
-    conv_set_sat_counter(n->sat, n->sat_checked);
     std::vector<unsigned> h(3 * nops, 0u);
     if (rc == ROMP_OK && hipMemcpyAsync(h.data(), d, 3 * nops * sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) { set_error("hipMemcpyAsync failed"); rc = ROMP_EHIP; }
     if (hipStreamSynchronize(st) != hipSuccess && rc == ROMP_OK) { set_error("hipStreamSynchronize failed"); rc = ROMP_EHIP; }
@@ -913,11 +895,9 @@ int romp_net_saturated(romp_net* n, int64_t* count_host, int reset, void* stream
 // Device address of the counter: romp_parse_watch reads it back with the detection counts (the API's default-on range guard).
 const int32_t* romp_net_sat_counter(romp_net* n) { return n ? (const int32_t*)n->sat : nullptr; }
 
-// 1: the fused BasicBlock kernels run their counting builds too (default: env ROMP_CHECK_FINITE=1; the API's range guard turns it on).
-int romp_net_set_sat_check(romp_net* n, int enable) {
+// Kept for ABI-5 hosts: it switched the fused BasicBlock kernels' counting builds on; every kernel counts in every build now.
+int romp_net_set_sat_check(romp_net* n, int) {
     ROMP_REQUIRE(n, "romp_net_set_sat_check: null net");
-    n->sat_checked = enable != 0;
-    drop_graphs(n);
     return ROMP_OK;
 }
 
@@ -943,10 +923,7 @@ void romp_net_destroy(romp_net* n) {
     for (float* p : n->bufs)
         if (p) hipFree(p);
     if (n->queues) hipFree(n->queues);
-    if (n->sat) {
-        if (conv_sat_counter() == n->sat) conv_set_sat_counter(nullptr, false);      // no launcher may keep a pointer into a dead net
-        hipFree(n->sat);
-    }
+    if (n->sat) hipFree(n->sat);
     if (n->plan_dev) hipFree(n->plan_dev);
     for (int l = 0; l < 2; ++l) {
         for (int k = 0; k < 3; ++k) {
@@ -967,10 +944,11 @@ void romp_net_destroy(romp_net* n) {
 int romp_conv_forward(const romp_op* op, const float* in, const float* res, float* out, int B, int mode, int variant,
                       void* stream) {
     ROMP_REQUIRE(op && in && out && B > 0, "romp_conv_forward: bad arguments");
-    conv_set_sat_counter(nullptr, false);              // a stand-alone layer belongs to no net: nothing to report to
-    if (op->kind == ROMP_OP_STEM) return launch_stem(*op, in, out, B, (hipStream_t)stream);
+    { const int rc = device_init(); if (rc) return rc; }
+    const LaunchCtx c{(hipStream_t)stream, nullptr, 0};    // a stand-alone layer belongs to no net: nothing to report to, no cap
+    if (op->kind == ROMP_OP_STEM) return launch_stem(*op, in, out, B, c);
     ROMP_REQUIRE(op->kind == ROMP_OP_CONV, "romp_conv_forward: op kind %d", op->kind);
-    return launch_conv(*op, in, res, out, B, mode, variant, nullptr, (hipStream_t)stream);
+    return launch_conv(*op, in, res, out, B, mode, variant, nullptr, c);
 }
 
 int romp_conv_num_variants(void) { return conv_num_variants(); }
@@ -980,26 +958,12 @@ int romp_conv_trace_read(unsigned long long* dst_host, int max_words) { return c
 
 int romp_conv_describe(const romp_op* op, int B, int variant, char* out, int n) {
     ROMP_REQUIRE(op && out && n > 0 && B > 0, "romp_conv_describe: bad arguments");
-    if (op->kind == ROMP_OP_STEM) { snprintf(out, n, "stem_conv"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_FUSESUM) { snprintf(out, n, "fusesum"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_FUSEUP) { snprintf(out, n, "fuseup"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_KSUM) { snprintf(out, n, "ksum"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_STEM7) { snprintf(out, n, "stem7_conv"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_MAXPOOL) { snprintf(out, n, "maxpool3s2"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_NOP) { snprintf(out, n, "nop"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_BBLOCK32) { snprintf(out, n, "bblock32"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_BBLOCK64) { snprintf(out, n, "bblock64"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_STEM2) { snprintf(out, n, "stem2"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_STEM7P) { snprintf(out, n, "stem7p"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_SEAM1X1) { snprintf(out, n, (op->flags & ROMP_OPF_SEAM_DS) ? "seam1x1_ds" : "seam1x1"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_FORK) { snprintf(out, n, "fork"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_JOIN) { snprintf(out, n, "join"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_RECORD) { snprintf(out, n, "record"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_WAIT) { snprintf(out, n, "wait"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_BEV_PACK) { snprintf(out, n, "bev_pack"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_BEV_MAPS) { snprintf(out, n, "bev_maps"); return ROMP_OK; }
-    if (op->kind == ROMP_OP_CONV3D) { snprintf(out, n, "conv3d"); return ROMP_OK; }
-    ROMP_REQUIRE(op->kind == ROMP_OP_CONV, "romp_conv_describe: op kind %d", op->kind);
+    const KindInfo* k = kind_info(op->kind);
+    ROMP_REQUIRE(k, "romp_conv_describe: op kind %d", op->kind);
+    if (op->kind != ROMP_OP_CONV) {
+        snprintf(out, n, "%s", (op->kind == ROMP_OP_SEAM1X1 && (op->flags & ROMP_OPF_SEAM_DS)) ? "seam1x1_ds" : k->name);
+        return ROMP_OK;
+    }
     if (variant >= 0 && !conv_variant_valid(*op, variant)) { set_error("variant %d not valid for this op", variant); return ROMP_EINVAL; }
     return describe_conv(*op, B, variant, out, n);
 }

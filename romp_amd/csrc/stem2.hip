@@ -256,7 +256,12 @@ __global__ __launch_bounds__(256, 1) void stem2_kernel(Stem2Params p) {
 }
 
 // `ops`: the stem op (kind NOP by now, fields intact) and conv2's op (kind ROMP_OP_STEM2): plan.fuse_stem2
-int launch_stem2(const romp_op& stem, const romp_op& op, const float* image, float* out, int B, hipStream_t st) {
+int setup_stem2() {
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S2Cfg::LDS_BYTES));
+    return ROMP_OK;
+}
+
+int check_stem2(const romp_op& stem, const romp_op& op) {
     ROMP_REQUIRE(stem.Cin == 3 && stem.Cout == 64 && stem.ksize == 3 && stem.stride == 2 && stem.weight && stem.scale && stem.shift,
                  "stem2: the op in front must hold the 3 -> 64 k3 s2 stem");
     ROMP_REQUIRE(op.ksize == 3 && op.stride == 2 && op.Cin == 64 && op.Cout == 64 && op.groups == 1 && op.relu && op.res_buf == ROMP_BUF_NONE &&
@@ -264,18 +269,11 @@ int launch_stem2(const romp_op& stem, const romp_op& op, const float* image, flo
                  "stem2: a 3x3 stride-2 64 -> 64 conv + ReLU with a per-wave f16x2 weight pack and an H2 output expected");
     ROMP_REQUIRE(op.H == stem.H / 2 && op.W == stem.W / 2 && stem.H % 64 == 0 && stem.W % 64 == 0, "stem2: %dx%d image: a multiple of 64 expected", stem.H, stem.W);
     ROMP_REQUIRE(((op.out_cstride | op.out_coff) & 7) == 0 && stem.act_shift == op.act_shift, "stem2: octet-aligned H2 output expected");
-    static bool attr = false;
-    static int num_cu = 256;
-    if (!attr) {
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S2Cfg::LDS_BYTES));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (image == nullptr && out == nullptr) return ROMP_OK;    // set-up only
+    return ROMP_OK;
+}
+
+int launch_stem2(const romp_op& stem, const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+    { const int rc = check_stem2(stem, op); if (rc) return rc; }
     Stem2Params p;
     memset(&p, 0, sizeof(p));
     p.image = image; p.w1 = stem.weight; p.scale1 = stem.scale; p.shift1 = stem.shift;
@@ -287,9 +285,9 @@ int launch_stem2(const romp_op& stem, const romp_op& op, const float* image, flo
     p.out_bs = op.out_bstride > 0 ? op.out_bstride : p.Ho * p.Wo * op.out_cstride;
     p.act_scale = ldexpf(1.f, op.act_shift);
     p.tiles_x = p.Wo / S2Cfg::TW; p.tiles_y = p.Ho / S2Cfg::TH; p.tiles_total = B * p.tiles_x * p.tiles_y;
-    p.sat = conv_sat_counter();
-    const int grid = p.tiles_total < num_cu ? p.tiles_total : num_cu;
-    hipLaunchKernelGGL(stem2_kernel, dim3((unsigned)grid), dim3(256), S2Cfg::LDS_BYTES, st, p);
+    p.sat = c.sat;
+    const int grid = p.tiles_total < device().num_cu ? p.tiles_total : device().num_cu;
+    hipLaunchKernelGGL(stem2_kernel, dim3((unsigned)grid), dim3(256), S2Cfg::LDS_BYTES, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

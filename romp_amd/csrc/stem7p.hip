@@ -283,35 +283,33 @@ __global__ __launch_bounds__(256, 2) void stem7p_kernel(Stem7pParams p) {
     if (p.out_h2) sat_report(p.sat, sat_mx);
 }
 
-int launch_stem7p(const romp_op& op, const float* image, float* out, int B, hipStream_t st) {
-    using X = S7Cfg;
+int setup_stem7p() {
+    ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem7p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S7Cfg::LDS_BYTES));
+    return ROMP_OK;
+}
+
+int check_stem7p(const romp_op& op) {
     ROMP_REQUIRE(op.Cin == 3 && op.Cout == 64 && op.ksize == 7 && op.stride == 2, "stem7p: expects 3->64 k7 s2 (+ max-pool 3 s2)");
     ROMP_REQUIRE(op.H % 32 == 0 && op.W % 32 == 0, "stem7p: input %dx%d must be a multiple of 32", op.H, op.W);
     ROMP_REQUIRE((op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0, "stem7p: output channels must be float4 aligned");
-    static bool attr = false;
-    static int num_cu = 256;
-    if (!attr) {
-        ROMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem7p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, X::LDS_BYTES));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ROMP_HIP_CHECK(hipGetDevice(&dev));
-        ROMP_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        attr = true;
-    }
-    if (image == nullptr && out == nullptr) return ROMP_OK;    // set-up only (outside any stream capture)
+    ROMP_REQUIRE(op.out_fmt != ROMP_FMT_H2 || ((op.out_cstride | op.out_coff) & 7) == 0, "stem7p: H2 output needs octet-aligned channels");
+    return ROMP_OK;
+}
+
+int launch_stem7p(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+    using X = S7Cfg;
+    { const int rc = check_stem7p(op); if (rc) return rc; }
     Stem7pParams p;
     memset(&p, 0, sizeof(p));
     p.image = image; p.w = op.weight; p.scale = op.scale; p.shift = op.shift; p.out = out;
     p.H = op.H; p.W = op.W; p.Hm = op.H / 2; p.Wm = op.W / 2; p.Ho = op.H / 4; p.Wo = op.W / 4;
     p.out_cs = op.out_cstride; p.out_co = op.out_coff;
     p.out_h2 = op.out_fmt == ROMP_FMT_H2; p.act_scale = ldexpf(1.f, op.act_shift);
-    ROMP_REQUIRE(!p.out_h2 || ((op.out_cstride | op.out_coff) & 7) == 0, "stem7p: H2 output needs octet-aligned channels");
-    p.sat = conv_sat_counter();
+    p.sat = c.sat;
     p.tiles_x = p.Wo / X::TW; p.tiles_y = p.Ho / X::TH; p.tiles_total = B * p.tiles_x * p.tiles_y;
-    long grid = 2L * num_cu;
+    long grid = 2L * device().num_cu;
     if (grid > p.tiles_total) grid = p.tiles_total;
-    hipLaunchKernelGGL(stem7p_kernel, dim3((unsigned)grid), dim3(256), X::LDS_BYTES, st, p);
+    hipLaunchKernelGGL(stem7p_kernel, dim3((unsigned)grid), dim3(256), X::LDS_BYTES, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

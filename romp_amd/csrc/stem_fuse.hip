@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(StemParams p) {
     sat_report(p.sat, sat_mx);
 }
 
-int launch_stem(const romp_op& op, const float* image, float* out, int B, hipStream_t st) {
+int launch_stem(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(op.Cin == 3 && op.Cout == 64 && op.ksize == 3 && op.stride == 2, "stem: expects 3->64 k3 s2");
     ROMP_REQUIRE(op.H % 32 == 0 && op.W % 32 == 0, "stem: input %dx%d must be a multiple of 32", op.H, op.W);
     ROMP_REQUIRE((op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0, "stem: output channels must be float4 aligned");
@@ -247,15 +247,15 @@ int launch_stem(const romp_op& op, const float* image, float* out, int B, hipStr
     p.H = op.H; p.W = op.W; p.Ho = op.H / 2; p.Wo = op.W / 2;
     p.out_cs = op.out_cstride; p.out_co = op.out_coff;
     p.out_h2 = op.out_fmt == ROMP_FMT_H2; p.act_scale = ldexpf(1.f, op.act_shift);
-    p.sat = conv_sat_counter();
+    p.sat = c.sat;
     ROMP_REQUIRE(!p.out_h2 || ((op.out_cstride | op.out_coff) & 7) == 0, "stem: H2 output needs octet-aligned channels");
     p.tiles_x = p.Wo / 16; p.tiles_y = p.Ho / 16;
     // ROMP_OPF_STEM_VALU (plan.Program.stem): the float32 VALU kernel for the H2 output too -- set by env ROMP_STEM=valu (A/B runs,
     // tests) and whenever 256 |w| would leave the fp16 pieces of the MFMA form (its 16x input / 256x weight scales are internal to
     // the kernel: x/255*2-1 lies in [-1, 1] whatever act_shift the OUTPUT tensor uses).
     const bool use_mfma = !(op.flags & ROMP_OPF_STEM_VALU);
-    if (p.out_h2 && use_mfma) hipLaunchKernelGGL(stem_mfma_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, st, p);
+    if (p.out_h2 && use_mfma) hipLaunchKernelGGL(stem_mfma_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, c.st, p);
+    else hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) void stem7_conv_kernel(Stem7Params p) {
     }
 }
 
-int launch_stem7(const romp_op& op, const float* image, float* out, int B, hipStream_t st) {
+int launch_stem7(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(op.Cin == 3 && op.Cout == 64 && op.ksize == 7 && op.stride == 2, "stem7: expects 3->64 k7 s2");
     ROMP_REQUIRE(op.H % 32 == 0 && op.W % 32 == 0, "stem7: input %dx%d must be a multiple of 32", op.H, op.W);
     ROMP_REQUIRE((op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0, "stem7: output channels must be float4 aligned");
@@ -346,7 +346,7 @@ int launch_stem7(const romp_op& op, const float* image, float* out, int B, hipSt
     p.H = op.H; p.W = op.W; p.Ho = op.H / 2; p.Wo = op.W / 2;
     p.out_cs = op.out_cstride; p.out_co = op.out_coff;
     p.tiles_x = p.Wo / 16; p.tiles_y = p.Ho / 16;
-    hipLaunchKernelGGL(stem7_conv_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(stem7_conv_kernel, dim3((unsigned)(B * p.tiles_x * p.tiles_y)), dim3(256), 0, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -376,13 +376,13 @@ __global__ void maxpool3s2_kernel(const float* __restrict__ in, int H, int W, in
     }
 }
 
-int launch_maxpool(const romp_op& op, const float* in, float* out, int B, hipStream_t st) {
+int launch_maxpool(const romp_op& op, const float* in, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(in && out && (op.Cin & 3) == 0 && (op.in_cstride & 3) == 0 && (op.out_cstride & 3) == 0 && !(op.H & 1) && !(op.W & 1),
                  "maxpool: bad shape");
     const size_t total = (size_t)B * (op.H / 2) * (op.W / 2) * (op.Cin / 4);
     size_t blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(maxpool3s2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, op.H, op.W, op.Cin / 4, op.in_cstride, out,
+    hipLaunchKernelGGL(maxpool3s2_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, in, op.H, op.W, op.Cin / 4, op.in_cstride, out,
                        op.out_cstride, total);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256) void fusesum_kernel(FuseParams p) {
 }
 
 int launch_fusesum(const FuseTerm* terms, int n_terms, float* out, int B, int H, int W, int C,
-                   int out_cstride, int out_coff, int relu, hipStream_t st, int out_fmt, int act_shift) {
+                   int out_cstride, int out_coff, int relu, const LaunchCtx& c, int out_fmt, int act_shift) {
     ROMP_REQUIRE(n_terms >= 1 && n_terms <= 4, "fusesum: %d terms unsupported", n_terms);
     ROMP_REQUIRE((C & 7) == 0 && (out_cstride & 3) == 0 && (out_coff & 3) == 0, "fusesum: channels must come in octets");
     FuseParams p;
@@ -481,7 +481,7 @@ int launch_fusesum(const FuseTerm* terms, int n_terms, float* out, int B, int H,
     p.out_h2 = out_fmt == ROMP_FMT_H2;
     ROMP_REQUIRE(!p.out_h2 || ((out_cstride | out_coff) & 7) == 0, "fusesum: H2 output needs octet-aligned channels");
     p.act_scale = ldexpf(1.f, act_shift); p.inv_act_scale = ldexpf(1.f, -act_shift);
-    p.sat = conv_sat_counter();
+    p.sat = c.sat;
     p.rows_total = B * H;
     const bool pow2 = (p.C8 & (p.C8 - 1)) == 0 && (W & (W - 1)) == 0;
     p.c8_shift = 0;
@@ -491,8 +491,8 @@ int launch_fusesum(const FuseTerm* terms, int n_terms, float* out, int B, int H,
     const int threads = per_row >= 256 ? 256 : (per_row >= 128 ? 128 : 64);
     int blocks = p.rows_total;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    if (pow2) hipLaunchKernelGGL(fusesum_kernel<1>, dim3((unsigned)blocks), dim3(threads), 0, st, p);
-    else hipLaunchKernelGGL(fusesum_kernel<0>, dim3((unsigned)blocks), dim3(threads), 0, st, p);
+    if (pow2) hipLaunchKernelGGL(fusesum_kernel<1>, dim3((unsigned)blocks), dim3(threads), 0, c.st, p);
+    else hipLaunchKernelGGL(fusesum_kernel<0>, dim3((unsigned)blocks), dim3(threads), 0, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }
@@ -570,7 +570,7 @@ __global__ __launch_bounds__(256) void ksum_kernel(KsumParams p) {
     if (p.out_h2) sat_report(p.sat, sat_mx);
 }
 
-int launch_ksum(const romp_op& op, const float* partial, const float* res, float* out, int B, hipStream_t st) {
+int launch_ksum(const romp_op& op, const float* partial, const float* res, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(partial && out && op.scale && op.shift, "ksum: null buffer");
     ROMP_REQUIRE(op.groups >= 1 && (op.Cout & 7) == 0 && op.in_cstride == op.groups * op.Cout, "ksum: partials must be %d x %d channels", op.groups, op.Cout);
     ROMP_REQUIRE(((op.out_cstride | op.out_coff) & 7) == 0 && (!res || ((op.res_cstride | op.res_coff) & 7) == 0), "ksum: channels must come in octets");
@@ -581,11 +581,11 @@ int launch_ksum(const romp_op& op, const float* partial, const float* res, float
     p.relu_from = op.relu ? op.relu_from : 0;
     p.res_h2 = op.res_fmt == ROMP_FMT_H2; p.out_h2 = op.out_fmt == ROMP_FMT_H2;
     p.act_scale = ldexpf(1.f, op.act_shift); p.inv_act_scale = ldexpf(1.f, -op.act_shift);
-    p.sat = conv_sat_counter();
+    p.sat = c.sat;
     p.total = (size_t)B * op.H * op.W * p.C8;
     size_t blocks = (p.total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(ksum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(ksum_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st, p);
     ROMP_HIP_CHECK(hipGetLastError());
     return ROMP_OK;
 }

@@ -243,6 +243,29 @@ def test_conv_describe_every_op(program):
             assert buf.value
 
 
+def test_op_kind_names_are_pinned():
+    """romp_conv_describe's name of every op kind but ROMP_OP_CONV (whose name is its kernel variant's): profiles, tune tables and
+    RompNet.profile's class sums key on these strings.  Written out here, not read from the library."""
+    from romp_amd import lib as L
+    names = {1: 'stem_conv', 3: 'fusesum', 4: 'fork', 5: 'join', 6: 'bev_pack', 7: 'bev_maps', 8: 'conv3d', 9: 'stem7_conv',
+             10: 'maxpool3s2', 11: 'ksum', 12: 'nop', 13: 'bblock32', 14: 'bblock64', 15: 'seam1x1', 16: 'fuseup', 17: 'record',
+             18: 'wait', 19: 'stem2', 20: 'stem7p'}
+    assert sorted(names) == [k for k in range(1, 21) if k != L.OP_CONV]
+    h = L.load()
+    buf = C.create_string_buffer(128)
+    op = L.RompOp()
+    for kind, name in names.items():
+        op.kind, op.flags = kind, 0
+        L.check(h.romp_conv_describe(C.byref(op), 1, -1, buf, 128))
+        assert buf.value.decode() == name, (kind, buf.value)
+    op.kind, op.flags = L.OP_SEAM1X1, L.OPF_SEAM_DS
+    L.check(h.romp_conv_describe(C.byref(op), 1, -1, buf, 128))
+    assert buf.value.decode() == 'seam1x1_ds'
+    for kind in (0, 21, 99, -1):
+        op.kind, op.flags = kind, 0
+        assert h.romp_conv_describe(C.byref(op), 1, -1, buf, 128) == -1, kind        # ROMP_EINVAL
+
+
 def test_weight_packing_roundtrip():
     from romp_amd.plan import pack_conv_weight, conv_pads, fold_bn
     w = torch.randn(70, 34, 3, 3)

@@ -470,6 +470,110 @@ def _fused_basic_block(dev, B, H, Cc, impl, monkeypatch, W=None, run=True, ref_d
         lib.romp_net_destroy(h)
 
 
+def _block_chain(dev, B, H, n_blocks, monkeypatch):
+    """A conv producing an H2 tensor followed by `n_blocks` fused 32-channel BasicBlocks, each one's residual the tensor in front
+    of it (as _fused_basic_block's program, any number of blocks) -> (program, op array, input, torch's result on the CPU, the
+    last activation)."""
+    from romp_amd import lib as L
+    from romp_amd.plan import Program, Act, set_conv_math
+    monkeypatch.setenv('ROMP_FUSE_BLOCKS', 'all')
+    monkeypatch.setenv('ROMP_BBLOCK_RUN', '0')
+    Cc, n = 32, 1 + 2 * n_blocks
+    g = torch.Generator().manual_seed(100 * B + H + n)
+    x = torch.randn(B, H, H, Cc, generator=g)
+    ws = [torch.randn(Cc, Cc, 3, 3, generator=g) / (Cc * 9) ** 0.5 for _ in range(n)]
+    sc = [torch.rand(Cc, generator=g) + 0.5 for _ in range(n)]
+    sh = [torch.randn(Cc, generator=g) * 0.2 for _ in range(n)]
+
+    def cbr(t, i, res=None):
+        y = F.conv2d(t, ws[i], None, padding=1) * sc[i].view(1, -1, 1, 1) + sh[i].view(1, -1, 1, 1)
+        return torch.relu(y if res is None else y + res)
+    P = Program(dev)
+    set_conv_math(P, 'f16x2')
+    t = cbr(x.permute(0, 3, 1, 2), 0)
+    a = P.conv('c0', Act(L.BUF_IMAGE, Cc, H, H, Cc), [ws[0]], [sc[0]], [sh[0]], 3, 1, True)
+    for b in range(n_blocks):
+        i = 1 + 2 * b
+        t = cbr(cbr(t, i), i + 1, res=t)
+        m = P.conv('c%d' % i, a, [ws[i]], [sc[i]], [sh[i]], 3, 1, True)
+        a = P.conv('c%d' % (i + 1), m, [ws[i + 1]], [sc[i + 1]], [sh[i + 1]], 3, 1, True, res=a)
+    ops = P.op_array()
+    assert P.fused_blocks == n_blocks and [o.kind for o in P.ops] == [L.OP_CONV] + [L.OP_NOP, L.OP_BBLOCK32] * n_blocks, [o.kind for o in P.ops]
+    assert all(ops[i].weight_aux and ops[i].weight_h2 and (ops[i].flags & L.OPF_WAVE16) for i in range(1, n))
+    return P, ops, x, t.permute(0, 2, 3, 1).contiguous(), a
+
+
+def test_both_bblock32_kernels_in_one_program_graph_first(dev, monkeypatch):
+    """One program with BOTH kernels behind ROMP_OP_BBLOCK32 -- block A on conv_h2c.h's row-pipelined one (ROMP_OPF_WAVE16), block B
+    on conv_h2b.hip's v1 (the flag cleared, as test_fused_basic_block's 'v1' arm does) -- whose FIRST forward is a graph forward:
+    every launch is captured, so neither kernel's one-time set-up may be left to its first launch.  The graph replay, an eager
+    forward after it and torch on the CPU agree: bit-equal between the two, _fused_basic_block's 5e-5 of the output's magnitude
+    against torch."""
+    import ctypes as C
+    from romp_amd import lib as L
+    from romp_amd.plan import decode_h2
+    B, H = 2, 32
+    P, ops, x, ref, a = _block_chain(dev, B, H, 2, monkeypatch)
+    ops[3].flags &= ~L.OPF_WAVE16
+    ops[4].flags &= ~L.OPF_WAVE16
+    lib = L.load()
+    h = C.c_void_p()
+    sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
+    L.check(lib.romp_net_create(C.byref(h), ops, len(P.ops), sizes, len(P.buf_floats), B))
+    try:
+        xd = x.to(dev).contiguous()
+        dummy = torch.empty(16, device=dev)
+        n = P.buf_floats[a.buf] * B
+        got = []
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for graph in (1, 0):
+                L.check(lib.romp_net_set_graph(h, graph))
+                out = torch.empty(n, device=dev)
+                L.check(lib.romp_net_forward(h, L.ptr(xd), B, L.ptr(dummy), L.ptr(dummy), L.stream_ptr(dev)))
+                L.check(lib.romp_net_read_buffer(h, a.buf, B, L.ptr(out), n, L.stream_ptr(dev)))
+                s.synchronize()
+                got.append(decode_h2(out.cpu().reshape(B, H, H, 32)))
+        err = (got[0] - ref).abs().max().item() / ref.abs().max().item()
+        print(f'two fused BasicBlocks (row-pipelined, v1), graph first: relative err {err:.3e}')
+        assert torch.equal(got[0], got[1])
+        assert err < 5e-5, err
+    finally:
+        lib.romp_net_destroy(h)
+
+
+def test_each_net_reports_clamps_to_its_own_counter(dev, monkeypatch):
+    """Two nets driven alternately from one host thread: the launches of each report clamped values to THAT net's counter.  Net A's
+    input is far outside the range its H2 tensors hold (65504 / 2^act_shift: c0's epilogue and the block clamp), net B's is not."""
+    import ctypes as C
+    from romp_amd import lib as L
+    B, H = 1, 32
+    P, ops, x, _, _ = _block_chain(dev, B, H, 1, monkeypatch)
+    lib = L.load()
+    sizes = (C.c_int64 * len(P.buf_floats))(*P.buf_floats)
+    nets = [C.c_void_p(), C.c_void_p()]
+    try:
+        for h in nets:
+            L.check(lib.romp_net_create(C.byref(h), ops, len(P.ops), sizes, len(P.buf_floats), B))
+        dummy = torch.empty(16, device=dev)
+        xs = [(x * 1e6).to(dev).contiguous(), x.to(dev).contiguous()]
+        for rep in range(2):                                  # A, B, A, B
+            for h, xd in zip(nets, xs):
+                L.check(lib.romp_net_forward(h, L.ptr(xd), B, L.ptr(dummy), L.ptr(dummy), L.stream_ptr(dev)))
+        counts = []
+        for h in nets:
+            c = C.c_int64(-1)
+            L.check(lib.romp_net_saturated(h, C.byref(c), 0, L.stream_ptr(dev)))
+            counts.append(c.value)
+        print('saturation events: out-of-range net %d, in-range net %d' % tuple(counts))
+        assert counts[0] > 0 and counts[1] == 0, counts
+    finally:
+        for h in nets:
+            if h:
+                lib.romp_net_destroy(h)
+
+
 @pytest.mark.parametrize('CO,NUP,ND,H,B', [(32, 1, 1, 64, 1), (32, 2, 1, 64, 3), (32, 3, 1, 128, 2), (64, 1, 2, 32, 3), (64, 2, 2, 64, 2), (128, 1, 3, 32, 3)])
 def test_fuseup(dev, CO, NUP, ND, H, B):
     _fuseup(dev, CO, NUP, ND, H, B)
