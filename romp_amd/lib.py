@@ -69,7 +69,7 @@ def load():
         from . import build as _build
         _build.build()
     lib = C.CDLL(LIB_PATH)
-    vp, i32, i64p, f = C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_float
+    vp, i32, i64p, f, d = C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_float, C.c_double
     sigs = {
         'romp_abi_version': (C.c_int, []),
         'romp_last_error': (C.c_char_p, []),
@@ -151,6 +151,14 @@ def load():
         'romp_track_assign': (C.c_int, [vp, i32, i32, C.c_double, vp, vp]),
         'romp_track_list': (C.c_int, [vp, vp, vp, vp]),
         'romp_oneeuro_smooth_frames': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, f, vp, vp, vp, vp, vp, vp, vp]),
+        'romp_mot_pack': (C.c_int, [i32, i32] + [C.POINTER(C.c_int32)] * 5 + [i64p, i32]),
+        'romp_mot_workspace_bytes': (C.c_int, [i64p, i64p]),
+        'romp_mot_boxes': (C.c_int, [vp, i32, i32, d, d, vp, vp]),
+        'romp_mot_tables': (C.c_int, [i64p, vp, vp, vp, vp, vp]),
+        'romp_mot_similarity': (C.c_int, [i64p, vp, vp, vp, vp, vp, i32, d, d, vp, d, vp, vp, vp, vp]),
+        'romp_mot_hota': (C.c_int, [i64p, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double), vp, vp, vp]),
+        'romp_mot_clear': (C.c_int, [i64p, vp, vp, vp, vp, d, vp, vp, vp]),
+        'romp_mot_identity': (C.c_int, [i64p, vp, vp, vp, vp, d, vp, vp, vp]),
     }
     # the version first: a stale or mismatched library must fail with THIS message, not with a missing-symbol AttributeError
     lib.romp_abi_version.restype = C.c_int
@@ -195,6 +203,9 @@ FIT_PRIOR_EXPORTS = ['romp_fit_pose_prior', 'romp_fit_joints3d']
 # OneEuro filters over what it reported
 TRACK_EXPORTS = ['romp_track_state_bytes', 'romp_track_init', 'romp_track_frames', 'romp_track_assign', 'romp_track_list',
                  'romp_oneeuro_smooth_frames']
+# include/romp_hip_mot.h: tracking scores on the device (HOTA, CLEAR-MOT, Identity for many clips; the IoU blocks they read)
+MOT_EXPORTS = ['romp_mot_pack', 'romp_mot_workspace_bytes', 'romp_mot_boxes', 'romp_mot_tables', 'romp_mot_similarity', 'romp_mot_hota',
+               'romp_mot_clear', 'romp_mot_identity']
 
 
 def has_bf16x3():
