@@ -11,7 +11,8 @@ extern "C" {
 /* What Sim3DR.__call__ (renderer.py:128-135, rasterize_kernel.cpp _rasterize) decides per pixel, kept instead of
  * painted.  verts (n,nver,3), tris (ntri,3): n meshes of one topology painted in index order onto an h x w canvas,
  * each with a fresh z-buffer.  A pixel's winner is the highest mesh that covers it, inside that mesh the fragment of
- * greatest depth, the lowest triangle on equal depth -- the very winner whose colour romp_sim3dr_render_batch writes.
+ * greatest depth, the lowest triangle on equal depth (-0.0 and +0.0 are equal; a NaN depth or one not above -1e8 is no
+ * fragment) -- the very winner whose colour romp_sim3dr_render_batch writes.
  * Every output pointer may be null; every byte of a non-null output is written by the call:
  *   person_map (h,w) int32      mesh_ids[mesh] (mesh_ids null: mesh); background -1
  *   tri_map    (h,w) int32      winning triangle; -1

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void bev_nms_kernel(const float* __restrict__ 
         const int d = r % BD;
         const int b = r / BD;
         const float* vol = c3d + (size_t)b * BVOX;
-        bool is_max = true;                                // MaxPool3d(5,1,2): keep where max == value
+        bool is_max = true;                                // MaxPool3d(5,1,2): keep where max == value; a NaN tap makes the max NaN
         for (int dz = -2; dz <= 2 && is_max; ++dz) {
             const int zz = d + dz;
             if ((unsigned)zz >= (unsigned)BD) continue;
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void bev_nms_kernel(const float* __restrict__ 
                 for (int dx = -2; dx <= 2; ++dx) {
                     const int xx = w + dx;
                     if ((unsigned)xx >= (unsigned)BM) continue;
-                    if (vol[((size_t)zz * BM + yy) * BM + xx] > v) { is_max = false; break; }
+                    if (!(vol[((size_t)zz * BM + yy) * BM + xx] <= v)) { is_max = false; break; }
                 }
             }
         }

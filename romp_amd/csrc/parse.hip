@@ -39,17 +39,20 @@ __global__ __launch_bounds__(PARSE_THREADS) void parse_nms_topk_kernel(const flo
     for (int p = tid; p < NPIX; p += PARSE_THREADS) {
         const int y = p / MAP, x = p % MAP;
         const float v = s_map[p];
-        float m = v;                                   // MaxPool2d(5,1,2): implicit -inf padding
+        // MaxPool2d(5,1,2) (implicit -inf padding) == v, without forming the maximum: the pool hands a NaN on, so its result
+        // equals v exactly when every tap of the window, v itself included, is <= v -- one ordered compare per tap, false for a
+        // NaN on either side (fmaxf would drop the NaN and let the neighbours of a NaN pixel through)
+        bool is_max = true;
         for (int dy = -2; dy <= 2; ++dy) {
             const int yy = y + dy;
             if ((unsigned)yy >= (unsigned)MAP) continue;
             for (int dx = -2; dx <= 2; ++dx) {
                 const int xx = x + dx;
                 if ((unsigned)xx >= (unsigned)MAP) continue;
-                m = fmaxf(m, s_map[yy * MAP + xx]);
+                is_max &= s_map[yy * MAP + xx] <= v;
             }
         }
-        const float score = (m == v) ? v : v * 0.0f;   // det * (maxm == det).float()
+        const float score = is_max ? v : v * 0.0f;     // det * (maxm == det).float()
         if (score > thresh) {
             const int slot = atomicAdd(&s_count, 1);
             s_score[slot] = score;

@@ -7,11 +7,14 @@
 //
 // The reference is sequential (triangles in index order, strict `>` z-test, colour written on every
 // accepted fragment).  With alpha == 1 (the only value its Python passes) the final colour of a pixel is
-// the colour of the fragment with the greatest depth, ties going to the LOWEST triangle index -- an
-// order-free statement, so the device runs two passes: (1) one thread per triangle scans its bounding box
-// and atomicMax-es a 64-bit key {orderable depth, ~triangle} per pixel; (2) one thread per pixel recomputes
-// the winner's barycentric weights and writes the truncated uint8 colour.  Every float expression keeps
-// the reference's operation order with contraction off, so the image is BIT-IDENTICAL to the C++ one.
+// the colour of the fragment with the greatest depth, ties going to the LOWEST triangle index, where -0.0
+// and +0.0 are EQUAL depths as they are for the reference's `>` (and a NaN depth, or one not above -1e8, is
+// no fragment) -- an order-free statement, so the device runs two passes: (1) one thread per triangle scans
+// its bounding box and atomicMax-es a 64-bit key {orderable depth, ~triangle} per pixel, the depth's zero
+// taken as +0.0 in the key only; (2) one thread per pixel recomputes the winner's barycentric weights (and,
+// for the maps, its values: a -0.0 stays a -0.0 there) and writes the truncated uint8 colour.  Every float
+// expression keeps the reference's operation order with contraction off, so the image is BIT-IDENTICAL to
+// the C++ one.
 // Vertex normals: the reference accumulates face normals onto vertices in triangle order; here one thread
 // per vertex walks its (triangle, corner) incidence list in ascending order -- the same additions in the
 // same order.  Lighting: one workgroup per mesh (min / max reductions of norm_vertices in LDS).
@@ -181,10 +184,12 @@ __device__ __forceinline__ unsigned orderable(float d) {
 }
 
 // Key of mesh `mesh` (of 2^mbits), depth d, triangle t: later meshes win, then greater depth, then lower t.
+// orderable() tells -0.0 from +0.0, the reference's `>` does not: both zeros take the key of +0.0.
 __device__ __forceinline__ unsigned long long raster_key(int mesh, int mbits, float d, int t) {
     const unsigned long long top = mbits ? (unsigned long long)mesh << (64 - mbits) : 0ull;
     const unsigned long long tmask = (1ull << (32 - mbits)) - 1ull;
-    return top | ((unsigned long long)orderable(d) << (32 - mbits)) | (tmask - (unsigned)t);
+    const unsigned od = orderable(d == 0.f ? 0.f : d);
+    return top | ((unsigned long long)od << (32 - mbits)) | (tmask - (unsigned)t);
 }
 
 __device__ __forceinline__ void raster_triangle(const float* __restrict__ v, const int32_t* __restrict__ tri, int t, int mesh,

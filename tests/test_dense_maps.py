@@ -150,10 +150,35 @@ def crafted(name):
     if name == 'canvas_37x53':          # h * w = 1961: no multiple of the block of 256, eight blocks
         verts, tri, _, _ = SO.make_scene(seed=1, h=37, w=53, n=3, n_lat=6, n_lon=8)
         return _scene(verts, tri, 37, 53, c=3, seed=5)
+    # Depth edges: where an IEEE `>` and an integer key of the depth's bits could part ways.  Right triangles with integer corners
+    # and legs of 8 or 4 (a power of two: every weight is an exact multiple of 1/8 or 1/4).
+    nz, pz = -0.0, 0.0
+    if name == 'zero_signs':            # -0.0 == +0.0 for the z-test: the first one drawn stays, whichever sign it has
+        return _scene([[1, 1, nz], [9, 1, nz], [1, 9, nz], [3, 1, pz], [11, 1, pz], [3, 9, pz],
+                       [14, 14, pz], [6, 14, pz], [14, 6, pz], [12, 14, nz], [4, 14, nz], [12, 6, nz]],
+                      [[0, 1, 2], [3, 4, 5], [6, 7, 8], [9, 10, 11]])
+    if name == 'zero_underflow':        # z = the smallest denormal: w * z rounds to -0.0 for w <= 1/2, stays the denormal above
+        d = float(np.float32(-1.4e-45))
+        return _scene([[2, 2, d], [10, 2, d], [2, 10, d], [2, 2, pz], [10, 2, pz], [2, 10, pz]], [[0, 1, 2], [3, 4, 5]])
+    if name == 'depth_floor':           # the -1e8 floor of the z-buffer, infinities and NaN; six disjoint footprints
+        lo, inf, nan = float(F(-1e8)), float('inf'), float('nan')
+        up = float(np.nextafter(F(-1e8), F(0)))
+        return _scene([[0, 0, lo], [8, 0, lo], [0, 8, lo],                     # 0: exactly the floor: never above it
+                       [8, 8, up], [0, 8, up], [8, 0, up],                     # 1: one ulp above the floor
+                       [10, 0, -inf], [14, 0, -inf], [10, 4, -inf],            # 2
+                       [14, 4, 1], [10, 4, nan], [14, 0, 1],                   # 3: NaN at p1 only; 0 * NaN is NaN at every pixel
+                       [10, 6, inf], [14, 6, inf], [10, 10, inf],              # 4, 5: +inf twice over the same pixels
+                       [10, 6, inf], [14, 6, inf], [10, 10, inf],
+                       [1, 10, 5], [5, 10, 5], [1, 14, 5],                     # 6: finite, 7: +inf over it
+                       [1, 10, inf], [5, 10, inf], [1, 14, inf]],
+                      [[3 * t, 3 * t + 1, 3 * t + 2] for t in range(8)])
+    if name == 'zero_meshes':           # three meshes over the same pixels at z = +0, -0, +0: a later mesh wins whatever the signs
+        return _scene([[[3, 3, z], [11, 3, z], [3, 11, z]] for z in (pz, nz, pz)], [[0, 1, 2]])
     raise KeyError(name)
 
 
-CRAFTED = ['coplanar_tie', 'edge_vertex', 'zero_area', 'off_canvas', 'paint_order', 'canvas_37x53']
+CRAFTED = ['coplanar_tie', 'edge_vertex', 'zero_area', 'off_canvas', 'paint_order', 'canvas_37x53',
+           'zero_signs', 'zero_underflow', 'depth_floor', 'zero_meshes']
 
 
 # ------------------------------------------------------------------------------------------------ CPU
@@ -241,6 +266,33 @@ def test_crafted_scenes_say_what_they_are_built_for():
     r = crafted('paint_order')['ref']
     assert (r['depth_buffers'][0] > F(-1e8)).sum() > 0 and r['person_pixels'][0] == 0 and not r['vert_visible'][0].any()
     assert r['person_pixels'][1] == (r['mesh_map'] == 1).sum() > 50 and r['vert_visible'][1].all()
+    alone = lambda sc, t: raster_np(sc['verts'][0], sc['tri'][t:t + 1], 16, 16)               # triangle t with nothing else drawn
+    sc = crafted('zero_signs')
+    r, z = sc['ref'], sc['verts'][0, :, 2]
+    assert (z == 0).all() and np.signbit(z).tolist() == [True] * 3 + [False] * 6 + [True] * 3
+    for first, second in ((0, 1), (2, 3)):                                                    # the overlaps go to 0 and to 2
+        both = (alone(sc, first)[1] >= 0) & (alone(sc, second)[1] >= 0)
+        assert both.sum() > 10 and (r['tri_map'][both] == first).all() and (r['tri_map'] == second).any()
+    sc = crafted('zero_underflow')
+    r, tiny = sc['ref'], F(-1.4e-45)
+    d0, w0 = alone(sc, 0)[0], alone(sc, 0)[1] >= 0
+    assert tiny < 0 and tiny == np.nextafter(F(0), F(-1)) and w0.sum() == 36 and np.array_equal(w0, alone(sc, 1)[1] >= 0)
+    under, kept = w0 & (d0 == 0), w0 & (d0 == tiny)
+    assert under.sum() > 0 and kept.sum() > 0 and under.sum() + kept.sum() == 36 and np.signbit(d0[under]).all()
+    assert (r['tri_map'][kept] == 1).all() and (r['tri_map'][under] == 0).all()               # 0 > denormal, but not 0 > -0.0
+    assert same(r['attr_map'][:, :, 0][under], np.full(int(under.sum()), -0.0, F))            # and the map keeps the sign
+    r = crafted('depth_floor')['ref']
+    painted = [int((r['tri_map'] == t).sum()) for t in range(8)]
+    assert painted[:4] == [0, 36, 0, 0] and painted[4] > 0 and painted[5] == 0, painted
+    assert painted[7] > 0 and painted[6] + painted[7] == 10, painted                          # 7's edges are 0 * inf = NaN: 6 stays there
+    assert r['tri_map'][4, 14] == -1 and r['tri_map'][0, 0] == -1                             # the NaN triangle's p0, the floor's p0
+    assert np.isposinf(r['attr_map'][:, :, 0][r['tri_map'] == 4]).all() and np.isfinite(r['attr_map'][:, :, 0][r['tri_map'] == 1]).all()
+    sc = crafted('zero_meshes')
+    r = sc['ref']
+    assert np.signbit(sc['verts'][:, 0, 2]).tolist() == [False, True, False] and (sc['verts'][:, :, 2] == 0).all()
+    assert r['person_pixels'].tolist() == [0, 0, 36] and (r['mesh_map'] == 2).sum() == 36
+    two = maps_np(sc['verts'][:2], sc['tri'], 16, 16)
+    assert two['person_pixels'].tolist() == [0, 36] and np.array_equal(two['mesh_map'] == 1, r['mesh_map'] == 2)
     for name in CRAFTED:
         r = crafted(name)['ref']
         assert r['person_pixels'].sum() == (r['mesh_map'] >= 0).sum()

@@ -2,7 +2,7 @@
 operation (oracle/bev_kernels_ref.py) and the reference-made edge fixture tests/golden/bev_edges.npz: the 3x3x3 conv (impulse
 response bit-exact, random data inside a derived float32 bound, the refiner pair as the plan lowers it), the map builder and the
 Conv1d packer (bit-exact, strided inputs with poisoned padding), the 3-D parse at the volume's borders / the top-K cut / B > 64 /
-the candidate capacity, and the per-person regression on crafted camera triples.  The tests drive the existing C ABI only: one-
+the candidate capacity / NaN and infinite voxels (the cases of tests/test_parse_nonfinite.py), and the per-person regression on crafted camera triples.  The tests drive the existing C ABI only: one-
 or two-op programs through romp_net_create, and romp_bev_parse / romp_bev_regress directly.  They are written against the
 operations, not against today's kernel boundaries."""
 import ctypes as C
@@ -14,6 +14,7 @@ import torch
 
 from oracle import bev_kernels_ref as K
 from oracle import bev_oracle as BO
+import test_parse_nonfinite as NF
 
 pytestmark = pytest.mark.gpu
 
@@ -381,6 +382,20 @@ def test_parse_batch_of_70(dev):
     assert got[0] == 0
     want = BO.parse_3dcentermap(cm, 0.25, 64)
     assert np.bincount(want[0], minlength=B).tolist() == [min(c, 64) for c in counts]
+    _same(got, want)
+
+
+@pytest.mark.parametrize('name', NF.NAMES)
+def test_parse_nonfinite_volumes(dev, name):
+    """NaN, +inf and -inf voxels (tests/test_parse_nonfinite.py, where the oracle is pinned to the reference's own steps for these very
+    volumes): the pool hands a NaN on, so a peak within two voxels of one is NOT a detection -- a `neighbour > value` test alone would
+    keep it; a peak three away is; +inf peaks come first, by flat index among themselves; -inf changes nothing around it."""
+    cm, kept = NF.case_3d(name)
+    got = _parse(dev, cm, NF.THRESH, NF.MAX_PERSON)
+    assert got[0] == 0
+    want = BO.parse_3dcentermap(cm, NF.THRESH, NF.MAX_PERSON)
+    print('%s: %d rows, the oracle has %d' % (name, len(got[1]), len(want[0])))
+    assert sorted((int(b),) + tuple(r) for b, r in zip(want[0], want[1].tolist())) == kept
     _same(got, want)
 
 
