@@ -4,7 +4,8 @@
 Follows simple_romp/romp/utils.py: LowPassFilter :203-215, OneEuroFilter :217-245, create_OneEuroFilter :257-258,
 smooth_results :261-269, smooth_global_rot_matrix :188-192, batch_rodrigues / quat2mat :493-533; the matrix ->
 axis-angle step is romp_oracle.rotmat_to_quat / quat_to_angle_axis (utils.py:535-682).  float32 torch on the CPU.
-Pinned by tests/golden/temporal_seq.npz, produced by the reference's own functions (oracle/make_golden_temporal.py).
+Pinned by tests/golden/temporal_seq.npz, produced by the reference's own functions (oracle/make_golden_temporal.py),
+and at the root-rotation edges by tests/golden/temporal_edges.npz (oracle/make_golden_temporal_edges.py).
 """
 import numpy as np
 import torch
