@@ -139,6 +139,50 @@ def pa_pve(pred_verts, target_verts):
     return pa_mpjpe(pred_verts, target_verts)
 
 
+def _accel(joints, gt, links, vis, joint_inds):
+    import ctypes as C
+    joints = _f32(joints)
+    dev = joints.device
+    assert joints.dim() == 3 and joints.shape[2] == 3, 'joints are (N, J, 3): %s' % (tuple(joints.shape),)
+    N, J = joints.shape[:2]
+    gt = None if gt is None else _f32(gt, dev)
+    assert gt is None or gt.shape == joints.shape, 'gt %s against joints %s' % (tuple(gt.shape), tuple(joints.shape))
+    vis = _u8(vis, dev)
+    assert vis is None or tuple(vis.shape) == (N,), vis.shape
+    prev, nxt = (torch.as_tensor(t, device=dev).to(torch.int32).contiguous() for t in links)
+    assert tuple(prev.shape) == (N,) and tuple(nxt.shape) == (N,), 'links: one entry per row'
+    idx = None if joint_inds is None else [int(i) for i in (joint_inds.tolist() if hasattr(joint_inds, 'tolist') else joint_inds)]
+    K = J if idx is None else len(idx)
+    value = torch.empty(N, dtype=torch.float32, device=dev)
+    valid = torch.empty(N, dtype=torch.uint8, device=dev)
+    if dev.type != 'cuda':
+        raise L.RompHipError('the acceleration metric runs on the HIP device only (no CPU fallback); move the tensors to "cuda:N"')
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_clip_accel(L.ptr(joints), N, J, L.ptr(gt), L.ptr(vis), K, None if idx is None else (C.c_int32 * K)(*idx),
+                                         L.ptr(prev), L.ptr(nxt), L.ptr(value), L.ptr(valid), L.stream_ptr(dev)))
+    return value, valid
+
+
+def accel(joints, links, joint_inds=None):
+    """compute_accel (evaluation_matrix.py:424-435) along the links of a clip (``romp_amd.clip.clip_links``): joints (N,J,3),
+    links = (prev, next) -> (values (N,), valid (N,) uint8) on the device.  values[n] = the mean over the (picked) joints of
+    |J[prev n] - 2 J[n] + J[next n]| at a row with both links; 0 and valid 0 elsewhere.  In the units of the joints."""
+    return _accel(joints, None, links, None, joint_inds)
+
+
+def accel_error(pred, gt, links, vis=None, joint_inds=None):
+    """compute_error_accel (evaluation_matrix.py:437-465): the mean over the joints of the distance between the predicted and
+    the true acceleration.  vis (N,): a row counts when it and both its neighbours are visible, the rows the reference's
+    np.roll mask keeps.  -> (values (N,), valid (N,) uint8) on the device."""
+    return _accel(pred, gt, links, vis, joint_inds)
+
+
+def mean_accel(joints, links, gt=None, vis=None, joint_inds=None):
+    """The mean of ``accel`` (or, with gt, of ``accel_error``) over the valid rows: a 0-d device tensor, NaN without a valid row."""
+    value, valid = _accel(joints, gt, links, vis, joint_inds)
+    return value.sum() / valid.sum()                             # invalid rows hold 0
+
+
 class MeshEvaluator:
     """A running score over a dataset, kept on the device.
 

@@ -23,6 +23,11 @@ v = s y + c2 (batch_orth_proj); 'perspective': cam = cam_trans, p = X + cam, u =
   ``joints3d_loss``      autograd node around ``romp_fit_joints3d``: the distance to 3-D targets under the rule of calc_mpjpe /
                          align_by_parts (loss_funcs/keypoints_loss.py:64-82), squared and normalised as the 2-D term.
 ``KeypointFitter`` takes all three as further terms of its objective, one launch each per step.
+
+Given the ``links`` of a tracked clip (``romp_amd.clip.clip_links``) ``KeypointFitter`` also ties a row to the rows of the same
+track in the neighbouring frames: velocity and acceleration terms on joints, camera and betas and a first-order term on the
+joint rotations (include/romp_hip_fit_clip.h, csrc/fit_clip.hip), two more launches per step.  ``romp_amd.clip`` holds the
+links, the autograd nodes of these terms and ``refine_clip``.
 """
 import ctypes as C
 
@@ -164,6 +169,43 @@ def _joints3d(joints, trans, targets, conf, inds_c, align_c, sigma, weight, loss
                                            L.ptr(gj), L.ptr(gt), int(accumulate), L.ptr(history), int(row), L.stream_ptr(dev)))
 
 
+def _links(links, N, dev):
+    """(prev, next) of ``romp_amd.clip.clip_links`` -> two contiguous int32 (N,) tensors on the device of the fit."""
+    if not isinstance(links, (tuple, list)) or len(links) != 2:
+        raise ValueError('links must be the pair (prev, next) of romp_amd.clip.clip_links')
+    prev, nxt = (torch.as_tensor(t).to(dev).to(torch.int32).contiguous() for t in links)
+    if prev.shape != (N,) or nxt.shape != (N,):
+        raise ValueError('links: prev and next need one entry per row (%d), got %s and %s' % (N, tuple(prev.shape), tuple(nxt.shape)))
+    return prev, nxt
+
+
+def _clip_segment(x, grad, col_w=None, w_vel=0., w_acc=0., sigma_vel=0., sigma_acc=0., accumulate=0):
+    """One linear block of romp_fit_temporal: x and grad (N, ...) float32 device tensors, read as (N, cols)."""
+    return L.ClipSegment(x.data_ptr(), grad.data_ptr(), None if col_w is None else col_w.data_ptr(), int(np.prod(x.shape[1:])),
+                         float(w_vel), float(w_acc), float(sigma_vel), float(sigma_acc), int(accumulate))
+
+
+def _temporal(segs, links, N, loss, poses=None, joint_w=None, w_rot=0., sigma_rot=0., gp=None, accumulate=0, history=None, row=0,
+              term_w=None):
+    """romp_fit_temporal: segs a ctypes array of ``L.ClipSegment`` (or None), links = (prev, next) on the device."""
+    dev = loss.device
+    if dev.type != 'cuda':
+        raise L.RompHipError('the temporal terms run on the HIP device only (no CPU fallback); move the tensors to "cuda:N"')
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_fit_temporal(segs, 0 if segs is None else len(segs), L.ptr(links[0]), L.ptr(links[1]), int(N),
+                                           L.ptr(term_w), L.ptr(poses), L.ptr(joint_w), float(w_rot), float(sigma_rot), L.ptr(gp),
+                                           int(accumulate), L.ptr(loss), L.ptr(history), int(row), L.stream_ptr(dev)))
+
+
+def _pair(w, name):
+    """A (velocity, acceleration) weight pair; a number stands for the velocity weight alone."""
+    vel, acc = (w, 0.) if np.ndim(w) == 0 else w
+    vel, acc = float(vel), float(acc)
+    if not (vel >= 0 and acc >= 0):
+        raise ValueError('%s must not be negative' % name)
+    return vel, acc
+
+
 def _align(align_inds):
     """-> ctypes int32 array of the alignment keypoints, or None.  The C side checks range and repeats."""
     if align_inds is None:
@@ -274,11 +316,26 @@ class KeypointFitter(object):
     (steps + 1, N, 2), unweighted.  ``joints3d`` (N,K,3) given to ``fit`` adds  w_3d * (the loss of ``joints3d_loss``)  with
     ``sigma_3d`` and ``align_inds``, and ``loss3d_history`` (steps + 1, N), unweighted.  With the perspective camera the targets
     are camera-space points (the joints plus cam); with the weak camera they are in the frame of the joints.  ``kp2d`` may be
-    None when ``joints3d`` is given: the 2-D launch is skipped and ``loss_history`` is zeros."""
+    None when ``joints3d`` is given: the 2-D launch is skipped and ``loss_history`` is zeros.
+
+    Temporal smoothness terms (include/romp_hip_fit_clip.h), all off by default; they act when ``fit`` is given ``links``, the
+    (prev, next) row tables of ``romp_amd.clip.clip_links``, and tie a row to the rows of the same track in the neighbouring
+    frames.  Each (vel, acc) pair weighs  sum_n rho(|x[n] - x[prev n]|^2)  and  sum_n rho(|x[prev n] - 2 x[n] + x[next n]|^2);
+    a number stands for vel alone.
+    ``w_smooth_joints`` on the 71 joints the layer returns (213 columns; ``smooth_joint_inds`` picks joints, three columns of
+    weight one per picked joint).  These joints are in the BODY frame -- the layer's output before any camera -- so the term
+    smooths the articulated motion only; the motion of the root through the scene is the camera segment's business:
+    ``w_smooth_cam`` on the three camera columns.  ``w_smooth_betas``: velocity only, one shape per track.
+    ``w_smooth_pose`` weighs  sum_n rho(sum_j joint_w[j] |R_j(n) - R_j(prev n)|_F^2)  over the 24 joint rotations (``joint_w``
+    (24,) or None = ones), first order, free of the axis-angle wrap.  ``sigma_smooth`` > 0 makes rho Geman-McClure for all of
+    them.  With any of them on a step gains two launches (joints and camera before ``smpl_backward``, betas and rotations
+    after it) and the result ``smooth_history`` (steps + 1, N, L), unweighted: (vel, acc) columns for joints, cam and betas,
+    then one for the rotations, each present when its term is on."""
 
     def __init__(self, smpl, camera='weak', steps=30, lr=0.02, sigma=0., w_betas=1e-4, w_pose=1e-4, root_align=False,
                  focal=443.4, half=256., betas=(0.9, 0.999), eps=1e-8, pose_prior=None, w_gmm=0., w_angle=0., w_3d=1., sigma_3d=0.,
-                 align_inds=None):
+                 align_inds=None, w_smooth_pose=0., joint_w=None, w_smooth_joints=(0., 0.), smooth_joint_inds=None,
+                 w_smooth_cam=(0., 0.), w_smooth_betas=0., sigma_smooth=0.):
         self.smpl, self.camera, self.mode = smpl, camera, _mode(camera)
         self.steps, self.lr, self.sigma = int(steps), float(lr), float(sigma)
         self.w_betas, self.w_pose, self.root_align = w_betas, w_pose, bool(root_align)
@@ -289,6 +346,12 @@ class KeypointFitter(object):
             raise ValueError('steps must not be negative')
         if self.w_gmm < 0 or self.w_angle < 0 or self.w_3d < 0:
             raise ValueError('w_gmm, w_angle and w_3d must not be negative')
+        self.w_smooth_pose, self.joint_w, self.sigma_smooth = float(w_smooth_pose), joint_w, float(sigma_smooth)
+        self.w_smooth_joints, self.w_smooth_cam = _pair(w_smooth_joints, 'w_smooth_joints'), _pair(w_smooth_cam, 'w_smooth_cam')
+        self.w_smooth_betas, self.smooth_joint_inds = float(w_smooth_betas), smooth_joint_inds
+        if not (self.w_smooth_pose >= 0 and self.w_smooth_betas >= 0):
+            raise ValueError('w_smooth_pose and w_smooth_betas must not be negative')
+        self.smooth_on = max(self.w_smooth_pose, self.w_smooth_betas, *(self.w_smooth_joints + self.w_smooth_cam)) > 0
 
     @staticmethod
     def _weights(w, cols, dev, free=0):
@@ -304,24 +367,29 @@ class KeypointFitter(object):
             raise ValueError('a prior weight vector needs %d entries, got %d' % (cols, out.numel()))
         return out
 
-    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None):
+    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
         """The buffers of one fit and its two halves of a step (``_FitRun``); ``fit`` drives it."""
-        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d)
+        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links)
 
-    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None):
+    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
         """betas0 (N,n_betas), poses0 (N,72), cam0 (N,3) (`cam` or `cam_trans`, by the camera), kp2d (N,K,2) in the normalised
         frame (None: no 2-D term, joints3d is needed then), conf (N,K) or None, joint_inds: K joint indices of the 71 or None
         (= the first K); joints3d (N,K3,3) or None, conf3d (N,K3) or None, joint_inds3d likewise.  The inputs are not changed.
         -> dict(betas, poses, cam, verts, joints, loss_history (steps + 1, N)), device tensors; nothing is downloaded; with the
-        prior terms on also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N)."""
-        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d)
+        prior terms on also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N).
+        links: (prev, next), the row tables of ``romp_amd.clip.clip_links``, or None; with links and a smoothness weight above
+        zero the rows of a track are fitted together and smooth_history (steps + 1, N, L) is returned too."""
+        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links)
         for s in range(self.steps):
             run.evaluate(s)
             run.update(s + 1)
         run.evaluate(self.steps)
         run.prior(self.steps, accumulate=0)                           # the prior's last row; its gradient is not used
+        run.smooth_params(self.steps, accumulate=0)                   # likewise
         out = {'betas': run.betas, 'poses': run.poses, 'cam': run.cam, 'verts': run.verts, 'joints': run.joints,
                'loss_history': run.history}
+        if run.smooth_on:
+            out['smooth_history'] = torch.cat([h for h in (run.hist_eval, run.hist_upd) if h is not None], 2)
         if run.prior_on:
             out['prior_history'] = run.prior_history
         if run.targets3d is not None:
@@ -334,9 +402,11 @@ class _FitRun(object):
     romp_fit_reproject (loss into history[row], joint and camera gradients); update(step): smpl_backward from the joint
     gradients alone and romp_fit_adam over betas, poses and cam (step counts from 1).  With 3-D targets evaluate also runs
     romp_fit_joints3d onto the same gradients; with a prior term on update runs romp_fit_pose_prior between its two launches
-    (losses into prior_history[the row of the last evaluate])."""
+    (losses into prior_history[the row of the last evaluate]).  With links and a smoothness term on, evaluate ends with
+    romp_fit_temporal over the joints and the camera, onto the gradients smpl_backward and romp_fit_adam read, and update runs
+    it over the betas and the rotations between smpl_backward and romp_fit_adam."""
 
-    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d=None, conf3d=None, joint_inds3d=None):
+    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
         self.fitter, smpl = fitter, fitter.smpl
         self.dev = dev = smpl.shapedirs.device
         self.ctx = smpl._context()                                   # raises without a HIP device
@@ -374,9 +444,13 @@ class _FitRun(object):
         if self.prior_on:
             self.loss_prior, self.prior_history = torch.empty(N, 2, **f32), torch.empty(fitter.steps + 1, N, 2, **f32)
         self.row = 0
+        self.smooth_on = links is not None and fitter.smooth_on
+        self.seg_eval = self.seg_upd = self.hist_eval = self.hist_upd = None
+        if self.smooth_on:
+            self._smooth_setup(links, f32)
         # A step is bound by the host issuing its launches, so a fit with nothing but the old four entries keeps the old two
         # methods, test for test (profiles/fit_prior_latency.txt holds that step against the parent commit's).
-        if self.kp2d is not None and self.targets3d is None and not self.prior_on:
+        if self.kp2d is not None and self.targets3d is None and not self.prior_on and not self.smooth_on:
             self.evaluate, self.update = self._evaluate_2d, self._update_2d
         self.state = torch.zeros(2, N * (nb + 72 + 3), **f32)        # Adam's m and v of the three tensors
         self.poses_ref = self.poses.clone()
@@ -391,6 +465,51 @@ class _FitRun(object):
             self.segs[i] = L.FitSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
                                         None if ref is None or w is None else ref.data_ptr(), None if w is None else w.data_ptr(),
                                         N, p.shape[1])
+
+    def _smooth_setup(self, links, f32):
+        """The segment tables and loss buffers of the two romp_fit_temporal launches of a step."""
+        f, N, dev, rows = self.fitter, self.N, self.dev, self.fitter.steps + 1
+        self.links = _links(links, N, dev)
+        sig = f.sigma_smooth
+        self.col_w = None
+        if f.smooth_joint_inds is not None:
+            idx = torch.as_tensor([int(i) for i in f.smooth_joint_inds], dtype=torch.long)
+            if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= 71:
+                raise ValueError('smooth_joint_inds must name joints 0..70')
+            picked = torch.zeros(71, 3, dtype=torch.float32)
+            picked[idx] = 1.
+            self.col_w = picked.reshape(213).to(dev)
+        # gj is always written earlier in the step (by the 2-D or the 3-D term); gc only when one of them has a camera gradient
+        cam_written = self.kp2d is not None or (self.targets3d is not None and f.mode == 1)
+        segs = []
+        if max(f.w_smooth_joints) > 0:
+            segs.append(_clip_segment(self.joints, self.gj, self.col_w, f.w_smooth_joints[0], f.w_smooth_joints[1], sig, sig, 1))
+        if max(f.w_smooth_cam) > 0:
+            segs.append(_clip_segment(self.cam, self.gc, None, f.w_smooth_cam[0], f.w_smooth_cam[1], sig, sig, int(cam_written)))
+        if segs:
+            self.seg_eval = (L.ClipSegment * len(segs))(*segs)
+            self.loss_eval, self.hist_eval = torch.empty(N, 2 * len(segs), **f32), torch.empty(rows, N, 2 * len(segs), **f32)
+        self.rot_on = f.w_smooth_pose > 0
+        self.joint_w = None
+        if self.rot_on and f.joint_w is not None:
+            self.joint_w = _f32(f.joint_w, dev).reshape(-1)
+            if self.joint_w.numel() != 24:
+                raise ValueError('joint_w needs 24 entries, got %d' % self.joint_w.numel())
+        if f.w_smooth_betas > 0:
+            self.seg_upd = (L.ClipSegment * 1)(_clip_segment(self.betas, self.gb, None, f.w_smooth_betas, 0., sig, sig, 1))
+        cols = 2 * (self.seg_upd is not None) + self.rot_on
+        if cols:
+            self.loss_upd, self.hist_upd = torch.empty(N, cols, **f32), torch.empty(rows, N, cols, **f32)
+
+    def smooth_params(self, row, accumulate):
+        """romp_fit_temporal on the current betas and rotations: the losses into smooth_history[row], the gradients into (or
+        onto) those of betas and poses.  Nothing when both terms are off."""
+        if self.hist_upd is not None:
+            f = self.fitter
+            if self.seg_upd is not None:
+                self.seg_upd[0].accumulate = int(accumulate)
+            _temporal(self.seg_upd, self.links, self.N, self.loss_upd, self.poses if self.rot_on else None, self.joint_w,
+                      f.w_smooth_pose, f.sigma_smooth, self.gp if self.rot_on else None, accumulate, self.hist_upd, row)
 
     def _evaluate_2d(self, row):
         f, ra = self.fitter, int(self.fitter.root_align)
@@ -420,6 +539,8 @@ class _FitRun(object):
             cam = f.mode == 1
             _joints3d(self.joints, self.cam if cam else None, self.targets3d, self.conf3d, self.inds3d_c, self.align_c, f.sigma_3d,
                       f.w_3d, self.loss3d, self.gj, self.gc if cam else None, int(self.kp2d is not None), self.history3d, row)
+        if self.seg_eval is not None:
+            _temporal(self.seg_eval, self.links, self.N, self.loss_eval, history=self.hist_eval, row=row)
         self.row = row
 
     def update(self, step):
@@ -430,6 +551,7 @@ class _FitRun(object):
                                          L.ptr(self.gb), L.ptr(self.gp), st))
             if self.prior_on:
                 self.prior(self.row, accumulate=1)
+            self.smooth_params(self.row, accumulate=1)
             L.check(self.h.romp_fit_adam(self.segs, 3, f.lr, f.adam_betas[0], f.adam_betas[1], f.eps, int(step), st))
 
     def prior(self, row, accumulate):
@@ -468,6 +590,12 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
     the dict, device tensors, with smpl_thetas, smpl_betas, cam / cam_trans, verts, joints, pj2d, pj2d_org rewritten (by
     ``romp_project`` / ``romp_bev_project_verts``) and fit_loss (N,2): the 2-D loss before and after; with a prior term on
     also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N)."""
+    return _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf3d, joint_inds3d, None, fit_args)
+
+
+def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf3d, joint_inds3d, link_fn, fit_args):
+    """``refine_outputs``; link_fn(rows) -> the (prev, next) of the rows fitted together (rows: device indices into the dict's
+    persons, None = all of them), or link_fn = None for unrelated rows (``romp_amd.clip.refine_clip`` supplies it)."""
     from .post_parser import body_mesh_projection2image
     parser = getattr(model, 'smpl_parser', None)
     if parser is None:
@@ -479,12 +607,14 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
     kp = None if kp2d_org is None else keypoints_to_input_frame(_f32(kp2d_org, dev), pad)
     conf = None if conf is None else _f32(conf, dev)
     joints3d, conf3d = (None if t is None else _f32(t, dev) for t in (joints3d, conf3d))
-    extra = ('prior_history', 'loss3d_history')
+    extra = ('prior_history', 'loss3d_history', 'smooth_history')
     N = betas.shape[0]
     out = dict(outputs)
+    links_of = (lambda rows: None) if link_fn is None else link_fn
     if not is_bev:
         fitter = KeypointFitter(parser.smpl_model, camera='weak', **dict(dict(root_align=model.settings.root_align), **fit_args))
-        res = fitter.fit(betas, thetas, _f32(outputs['cam'], dev), kp, conf, joint_inds, joints3d, conf3d, joint_inds3d)
+        res = fitter.fit(betas, thetas, _f32(outputs['cam'], dev), kp, conf, joint_inds, joints3d, conf3d, joint_inds3d,
+                         links=links_of(None))
         proj = body_mesh_projection2image(res['joints'], res['cam'], input2org_offsets=pad)
         out.update({'smpl_betas': res['betas'], 'smpl_thetas': res['poses'], 'cam': res['cam'], 'cam_trans': proj['cam_trans'],
                     'verts': res['verts'], 'joints': res['joints'], 'pj2d': proj['pj2d'], 'pj2d_org': proj['pj2d_org'],
@@ -508,7 +638,7 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
         group_args = dict(args, pose_prior=None) if layer is parser.smil_model else args
         res = KeypointFitter(layer, camera='perspective', **group_args).fit(
             betas[rows][:, :nb], thetas[rows], trans[rows], pick(kp, rows), pick(conf, rows), joint_inds, pick(joints3d, rows),
-            pick(conf3d, rows), joint_inds3d)
+            pick(conf3d, rows), joint_inds3d, links=links_of(rows))
         new['smpl_betas'][rows, :nb] = res['betas']
         for key in extra:                                             # (steps + 1, n, ...) of this group into (steps + 1, N, ...)
             if key in res:

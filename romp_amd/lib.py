@@ -51,6 +51,12 @@ class FitSegment(C.Structure):
                 ('prior_ref', C.c_void_p), ('prior_w', C.c_void_p), ('rows', C.c_int32), ('cols', C.c_int32)]
 
 
+class ClipSegment(C.Structure):
+    """Mirror of `struct romp_clip_segment` (include/romp_hip_fit_clip.h): one linear block of a romp_fit_temporal call."""
+    _fields_ = [('x', C.c_void_p), ('grad', C.c_void_p), ('col_w', C.c_void_p), ('cols', C.c_int32), ('w_vel', C.c_float),
+                ('w_acc', C.c_float), ('sigma_vel', C.c_float), ('sigma_acc', C.c_float), ('accumulate', C.c_int32)]
+
+
 _lib = None
 
 
@@ -145,6 +151,8 @@ def load():
         'romp_fit_pose_prior': (C.c_int, [vp, i32, vp, vp, vp, i32, i32, f, f, vp, vp, vp, i32, vp, i32, vp]),
         'romp_fit_joints3d': (C.c_int, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, f, f, vp, vp, vp,
                                         i32, vp, i32, vp]),
+        'romp_fit_temporal': (C.c_int, [C.POINTER(ClipSegment), i32, vp, vp, i32, vp, vp, vp, f, f, vp, i32, vp, vp, i32, vp]),
+        'romp_clip_accel': (C.c_int, [vp, i32, i32, vp, vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp]),
         'romp_track_state_bytes': (C.c_int, [i32]),
         'romp_track_init': (C.c_int, [vp, i32, i32, f, f, C.c_double, i32, C.c_double, vp]),
         'romp_track_frames': (C.c_int, [vp, vp, vp, C.POINTER(C.c_int32), i32, vp, vp, vp, vp, vp, i32, vp]),
@@ -199,6 +207,8 @@ SMPL_GRAD_EXPORTS = ['smpl_backward']
 FIT_EXPORTS = ['romp_fit_reproject', 'romp_fit_adam']
 # include/romp_hip_fit_priors.h: SMPLify's pose priors (max-mixture GMM, joint angles) and 3-D joint targets for the same fit
 FIT_PRIOR_EXPORTS = ['romp_fit_pose_prior', 'romp_fit_joints3d']
+# include/romp_hip_fit_clip.h: temporal smoothness terms over the links of a tracked clip for the same fit, and the acceleration metric
+FIT_CLIP_EXPORTS = ['romp_fit_temporal', 'romp_clip_accel']
 # include/romp_hip_track.h: ByteTrack-3D association on the device (the tracker, its assignment alone, the track lists) and the
 # OneEuro filters over what it reported
 TRACK_EXPORTS = ['romp_track_state_bytes', 'romp_track_init', 'romp_track_frames', 'romp_track_assign', 'romp_track_list',
