@@ -73,17 +73,32 @@ __device__ __forceinline__ void conv_args_now(const ConvParams& p) {
 // activation ranges (plan.assign_formats, romp_net_range_scan), the clamp is what keeps an unforeseen outlier finite.
 constexpr float H2_MAX = 65504.f;
 __device__ __forceinline__ float h2_sat(float x) { return __builtin_fminf(__builtin_fmaxf(x, -H2_MAX), H2_MAX); }
-// Saturation is OBSERVABLE: every site that clamps keeps a per-lane running max of |value before the clamp| (one
-// v_max3_f32 per two values) and reports once per wave and work item -- sat_report -- into the net's device counter
-// (romp_net_saturated; RompNet.saturated), which every launcher copies from its LaunchCtx into its parameters.
-__device__ __forceinline__ void sat_track(float& mx, float a, float b) { mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b))); }
+// Saturation is OBSERVABLE: every site that clamps keeps a per-lane running max of |value| (v_maximum3_f32: one per
+// two values where the calls chain on mx, three per four where the compiler pairs two calls first) and reports once per wave and
+// work item -- sat_report -- into the net's device counter (romp_net_saturated; RompNet.saturated), which every launcher copies
+// from its LaunchCtx into its parameters.  The sites come in three forms
+// ("the three forms of a clamp site"):
+//   float form, tracked BEFORE the clamp (write_pieces, h2_pack, stem7p): reports |value| >= 65504, i.e. every clamped value and a
+//     value that is exactly the limit;
+//   float form, tracked AFTER the clamp (the direct epilogue, conv_h2k, seam1x1, the MFMA stem): |value| == 65504 iff it was clamped
+//     or was exactly the limit -- the same set;
+//   packed form (sat_track_pk below): conservative by one fp16 ulp.
+// The maximum PROPAGATES a NaN (v_maximum3_f32, new in gfx950; fmaxf would drop it) and sat_report tests !(mx < limit): a NaN on its
+// way into the pieces -- h2_sat turns it into the finite -65504 -- is reported like a clamp.  (A NaN in front of a ReLU is 0 after it
+// in the float32 kernels too, and is not a clamp.)
+__device__ __forceinline__ void sat_track(float& mx, float a, float b) {
+    mx = __builtin_elementwise_maximum(mx, __builtin_elementwise_maximum(__builtin_fabsf(a), __builtin_fabsf(b)));
+}
 __device__ __forceinline__ void sat_report(int* counter, float mx) {
-    if (counter && __builtin_amdgcn_ballot_w64(mx >= H2_MAX) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(counter, 1);
+    if (counter && __builtin_amdgcn_ballot_w64(!(mx < H2_MAX)) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(counter, 1);
 }
 // The packed form for POST-ReLU values (non-negative; round 6): the running per-half maximum of the HIGH-piece dwords a kernel has
 // just formed -- v_pk_maximum3_f16, new in gfx950: ONE instruction per two dwords = four values (the float32 form above is one per
 // two; the fused BasicBlock kernels' counting builds used one per value and cost 1.7-2 % of the job, profiles/r06_guard_cost.txt).
-// A half reads 0x7BFF (65504) iff its value was clamped, 0x7E00 if it was a NaN: either is reported.
+// A half reads 0x7BFF (65504) if its value was clamped -- and also if an UNCLAMPED value in (65488, 65504] rounded up to it: the form
+// is conservative by one fp16 ulp, it reports every clamp and, besides, values within 16 of the limit.  (A NaN high piece, 0x7E00,
+// would pass sat_report_pk's test as well; every site of this form makes its pieces from relu(...) -- fmaxf / v_med3 turn a NaN
+// into 0 first, as the float32 kernels' ReLU does -- so no input reaches that arm and no test exercises it.)
 __device__ __forceinline__ unsigned sat_track_pk(unsigned mx, unsigned h0, unsigned h1) {
     unsigned d;
     asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(mx), "v"(h0), "v"(h1));
