@@ -60,7 +60,8 @@ int  romp_mot_tables(const int64_t* block, const int64_t* block_dev, const int32
 
 /* The IoU blocks.  gt_boxes (gt rows, 4) float32 = x, y, w, h.  Predictions: pred_boxes (pred rows, 4) float32, or -- pred_boxes NULL
  * -- pred_kp2d (pred rows, J, 2) float32, boxed as romp_mot_boxes does.  IoU = intersection / union, 0 where the union is 0; an IoU
- * with 1 - IoU > max_iou is set to 0; a pair with an unused row is 0.  Also rowsum[gt rows] and colsum[pred rows] of each block,
+ * with 1 - IoU > max_iou is set to 0; a pair with an unused row is 0, and so is a pair with a box that has a NaN or infinite
+ * coordinate (given as a box; joints are boxed with fmin / fmax, which pass over a NaN).  Also rowsum[gt rows] and colsum[pred rows] of each block,
  * summed in index order.  One workgroup per frame, one thread per pair. */
 int  romp_mot_similarity(const int64_t* block, const int64_t* block_dev, const float* gt_boxes, const int32_t* gt_ids,
                          const float* pred_boxes, const float* pred_kp2d, int J, double enlarge_x, double enlarge_y,

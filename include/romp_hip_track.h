@@ -12,7 +12,12 @@
  * twice that, only when some weak detection exists; tentative x leftover at three times), kf_correct / absorb, births (confirmed
  * only on frame 1), the lost-track timeout (a timed-out track leaves the lost list one frame later), the tracked and lost lists
  * rebuilt in the order of union / minus, duplicate removal (a live and a lost track closer than dup_thresh in (x, y): the
- * younger by frame - born goes) and nearest_detection (first minimum over all rows of the frame).
+ * younger by frame - born goes; at equal age the live one) and nearest_detection (first minimum over all rows of the frame).
+ *
+ * Non-finite input (the host tracker raises on it): a row with a NaN or infinite coordinate stays alone.  Every distance to it is
+ * not comparable, which the assignment takes as a forbidden pair; with a strong score it begins a tentative track that nothing
+ * matches and that is removed a frame later, as a far-away detection would; and it is never reported as the nearest detection of
+ * a finite track, at whichever row it stands.  A NaN score is neither strong nor weak: the row takes part in no association.
  *
  * State: ONE caller-owned device buffer of romp_track_state_bytes(capacity) bytes, 8-byte aligned:
  *   int32 header[32]   [0] capacity  [1] frame id  [2] last id  [3] number tracked  [4] number lost  [5] overflow count

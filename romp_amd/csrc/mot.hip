@@ -126,6 +126,10 @@ __device__ __forceinline__ int wave_count_valid(int lane, const int32_t* __restr
     return c;
 }
 
+// A box with a NaN or infinite coordinate is similar to nothing (iou_host gives 0 there: numpy's minimum and maximum hand a NaN on,
+// fmin and fmax would drop it and score the rest of the box)
+__device__ __forceinline__ bool finite_box(const double* b) { return isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]); }
+
 __device__ __forceinline__ void box_of_joints(const float* __restrict__ kp, int J, double ex, double ey, double* box) {
     double x0 = (double)kp[0], x1 = x0, y0 = (double)kp[1], y1 = y0;
     for (int j = 1; j < J; ++j) {
@@ -180,12 +184,12 @@ __global__ __launch_bounds__(NT) void mot_similarity_kernel(const int64_t* __res
     const int n = (int)(M.gt_off[f + 1] - go), m = (int)(M.pred_off[f + 1] - po);
     for (int r = tid; r < n; r += NT) {
         for (int k = 0; k < 4; ++k) gb[4 * r + k] = (double)gt_boxes[(go + r) * 4 + k];
-        gv[r] = valid_id(gt_ids[go + r], G);
+        gv[r] = valid_id(gt_ids[go + r], G) && finite_box(gb + 4 * r);
     }
     for (int c = tid; c < m; c += NT) {
         if (pred_boxes) for (int k = 0; k < 4; ++k) pb[4 * c + k] = (double)pred_boxes[(po + c) * 4 + k];
         else box_of_joints(pred_kp2d + (po + c) * J * 2, J, ex, ey, pb + 4 * c);
-        pv[c] = valid_id(pred_ids[po + c], K);
+        pv[c] = valid_id(pred_ids[po + c], K) && finite_box(pb + 4 * c);
     }
     __syncthreads();
     for (int idx = tid; idx < n * m; idx += NT) {

@@ -349,15 +349,16 @@ __global__ __launch_bounds__(NT) void track_frames_kernel(unsigned char* __restr
             n_tracked = L.n[11]; n_lost = L.n[12]; nout = L.n[13];
             for (int k = tid; k < n_tracked; k += NT) L.keep[L.tracked[k]] = 1;
             for (int k = tid; k < n_lost; k += NT) L.keep[L.lost[k]] = 1;
-            // ---- what is reported: the confirmed tracks, each with the nearest detection of the frame (first minimum)
+            // ---- what is reported: the confirmed tracks, each with the nearest detection of the frame (first minimum).  A row with a
+            // non-finite coordinate is at no comparable distance, wherever it stands: it is never the nearest of a finite track
             for (int k = tid; k < nout; k += NT) {
                 const int slot = L.pool[k];
                 const Slot& s = tab[slot];
-                double bd = 0.;
+                double bd = INFINITY;
                 int bi = 0;
                 for (int i = 0; i < N; ++i) {
                     const double d = dist4(L.pts + 4 * i, s.mean);
-                    if (i == 0 || d < bd) { bd = d; bi = i; }
+                    if (d < bd) { bd = d; bi = i; }
                 }
                 out_ids[(size_t)t * cap + k] = s.id;
                 out_rows[(size_t)t * cap + k] = row0 + bi;

@@ -125,6 +125,18 @@ def build_clips():
     clips['seed7'] = clip(*walk(11, 7, 5, 3, 0.1, 0.1))
     clips['seed7_kp2d'] = clip(*walk(11, 7, 5, 3, 0.1, 0.1), kp2d=True, seed=11)
     clips['seed40'] = clip(*walk(12, 40, 4, 6, 0.15, 0.05))
+    # the caps: four frames of 256 x 256 rows (persons on a grid, disjoint, the predictions a few pixels off, both sides shuffled) and
+    # 512 ids a side -- the even frames hold one half of them, the odd frames the other; from frame 2 on every 37th prediction
+    # carries an id of the other half.  Identity's assignment is 512 x 512.
+    rs = np.random.RandomState(3)
+    P = 256
+    base = np.stack([(np.arange(P) % 16) * 100., (np.arange(P) // 16) * 200., np.full(P, 60.), np.full(P, 150.)], 1)
+    gt, pred = [], []
+    for t in range(4):
+        off = 0 if t % 2 == 0 else P
+        gt.append((t, [(off + i, base[i]) for i in rs.permutation(P)]))
+        pred.append((t, [((off + i) if not (t >= 2 and i % 37 == 0) else 2 * P - 1 - (off + i), base[i] + rs.randn(4) * 3) for i in rs.permutation(P)]))
+    clips['caps'] = clip(gt, pred)
     return clips
 
 
@@ -172,6 +184,15 @@ def main(trackeval_dir):
                  res['CLEAR']['MOTA'], res['CLEAR']['IDSW'], res['CLEAR']['Frag'], res['CLEAR']['MT'], res['CLEAR']['PT'], res['CLEAR']['ML'],
                  res['Identity']['IDF1']))
     path = os.path.join(ROOT, 'tests', 'golden', 'mot_metrics.npz')
+    if os.path.exists(path):                              # a clip that is added changes nothing that is there: every stored array but the list of names
+        with np.load(path) as old:
+            for k in old.files:
+                if k == 'names':
+                    assert set(old[k].tolist()) <= set(out[k].tolist()), 'a clip of the fixture is gone'
+                else:
+                    assert k in out and old[k].dtype == out[k].dtype and old[k].shape == out[k].shape and \
+                        old[k].tobytes() == out[k].tobytes(), 'the stored array %s would change' % k
+            print('every array of the %d stored clips is reproduced bit for bit' % len(old['names']))
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), 'bytes')
 

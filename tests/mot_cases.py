@@ -27,14 +27,23 @@ def load():
     return _cache['v']
 
 
-def reference_bound():
+def reference_bound(only=None):
     """TrackEval keeps HOTA's arrays in float32: a sum of n terms carries up to n roundings of 2^-24 relative (all terms are >= 0).
     Its longest sum is LocA's, one similarity per matched pair, so at most min(ground-truth rows, predicted rows) terms; the largest
     such clip of the fixture sets n.  Four more roundings for a final field: the division, the product and the root of
-    HOTA = sqrt(DetA * AssA), and the store."""
+    HOTA = sqrt(DetA * AssA), and the store.
+
+    The bound grows with the clips it covers, so `only` (a list of clip names) keeps it to those: the cap-sized clip 'caps' (1024
+    rows a side, (1024 + 4) 2^-24 = 6.1e-5) is held to its own bound, every other clip to the bound of the others, (146 + 4) 2^-24."""
     names, args, _, _ = load()
-    n = max(min(len(args[k]['gt_ids']), len(args[k]['pred_ids'])) for k in names)
+    n = max(min(len(args[k]['gt_ids']), len(args[k]['pred_ids'])) for k in (names if only is None else only))
     return (n + 4) * 2.0 ** -24
+
+
+def bound_of(name):
+    """The bound a clip is held to: its own for 'caps', that of all the other clips for any other."""
+    names = load()[0]
+    return reference_bound([name] if name == 'caps' else [k for k in names if k != 'caps'])
 
 
 def against_reference(got, want, bound):

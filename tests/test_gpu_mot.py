@@ -3,7 +3,12 @@ values recorded from the reference's TrackEval (golden/mot_metrics.npz, tests/ma
 
 Similarity: 1e-12 against a float64 numpy IoU (absolute for the IoU, which is at most 1; relative for the row and column sums).
 Summary against the host mirror: counts equal, floats within 1e-12 relative -- both sides are float64 and differ only in the order
-of their sums.  Summary against the recorded reference: mot_cases.reference_bound(), as in test_mot.py.
+of their sums.  Summary against the recorded reference: mot_cases.reference_bound(), as in test_mot.py (mot_cases.bound_of: the
+cap-sized clip 'caps' under its own bound, every other clip under the bound of the others).
+
+Through the ABI directly (pack_layout + score_clips): rows that take part in nothing (id -1, id >= the clip's id count, an id count
+that is never reached), a clip of zero frames between two others, and boxes with a NaN or +-inf coordinate, which are similar to
+nothing -- as iou_host has it (test_mot.py).
 """
 import ctypes as C
 import os
@@ -44,13 +49,15 @@ def _evaluator(dev, names):
 
 
 def _check(got, names, host):
-    bound, worst_host, worst_ref = MC.reference_bound(), 0., 0.
+    worst_host, worst_ref = 0., 0.
     assert sorted(got['clips']) == sorted(names)
     for n in names:
         diff = M._compare(got['clips'][n], host[n], 1e-12)
         assert diff is None, (n, diff)
-        worst_ref = max(worst_ref, MC.against_reference(got['clips'][n], REF[n], bound))
-        worst_host = max(worst_host, MC.against_reference(got['clips'][n], host[n], 1e-12))
+        to_ref, to_host = MC.against_reference(got['clips'][n], REF[n], MC.bound_of(n)), MC.against_reference(got['clips'][n], host[n], 1e-12)
+        if n == 'caps':
+            print('caps: largest relative gap %.3g to the host mirror, %.3g to TrackEval (bound %.3g)' % (to_host, to_ref, MC.bound_of(n)))
+        worst_ref, worst_host = max(worst_ref, to_ref), max(worst_host, to_host)
     ref, comb = M.combine_clips({n: host[n] for n in names})
     assert M._compare(got['combined'], comb, 1e-12) is None
     for k in ref:
@@ -105,6 +112,7 @@ def test_all_box_clips_in_one_call(dev, host):
     worst_host, worst_ref = _check(got, BOXES, host)
     print('summary() of %d clips: %d launches, %d bytes downloaded; largest relative gap %.3g to the host mirror, %.3g to TrackEval (bound %.3g)'
           % (len(BOXES), ev.last_launches, ev.last_download_bytes, worst_host, worst_ref, MC.reference_bound()))
+    assert 'caps' in BOXES and len(BOXES) == 12
     assert ev.last_launches == 9 and ev.last_download_bytes == 8 * len(BOXES) * (19 * 7 + 12 + 3 + 1)
 
 
@@ -119,6 +127,119 @@ def test_three_clips_of_1_7_and_40_frames(dev, host):
     _check(_evaluator(dev, names).summary(), names, host)
     names = ['seed7_kp2d', 'no_pred']                           # kp2d predictions next to a clip without any
     _check(_evaluator(dev, names).summary(), names, host)
+
+
+# ------------------------------------------------------------------------------------------------ through the ABI directly
+def _layout(clips, n_pred_ids=None):
+    """Prepared clips -> (block, the five device-side arrays as numpy)."""
+    clip_frames = np.concatenate([[0], np.cumsum([c['T'] for c in clips])])
+    go = np.concatenate([[0], np.cumsum(np.concatenate([c['gt_rows'] for c in clips]))]).astype(np.int64)
+    po = np.concatenate([[0], np.cumsum(np.concatenate([c['pred_rows'] for c in clips]))]).astype(np.int64)
+    block = M.pack_layout(clip_frames, go, po, [c['n_gt_ids'] for c in clips], n_pred_ids or [c['n_pred_ids'] for c in clips])
+    cat = lambda k, dt, tail: np.ascontiguousarray(np.concatenate([np.asarray(c[k], dt).reshape((-1,) + tail) for c in clips]), dt)  # noqa: E731
+    return block, go, po, cat('gt_boxes', np.float32, (4,)), cat('gt_ids', np.int32, ()), cat('pred_ids', np.int32, ()), cat('pred_boxes', np.float32, (4,))
+
+
+def _score(dev, block, gb, gi, pi, pb, metrics=True):
+    up = lambda x: torch.from_numpy(x).to(dev)  # noqa: E731
+    r = M.score_clips(dev, block, up(gb), up(gi), up(pi), up(pb), None, metrics=metrics, **SETTINGS)
+    return {k: r[k].cpu().numpy() for k in ('sim', 'rowsum', 'colsum') + (('hota', 'clear', 'identity') if metrics else ())}
+
+
+def _fields(r, s, n_gt_ids):
+    return {'HOTA': M._hota_fields(*(r['hota'][s][:, i] for i in range(M.HOTA_OUT))),
+            'CLEAR': M._clear_fields(*r['clear'][s].tolist(), num_gt_ids=n_gt_ids), 'Identity': M._identity_fields(*r['identity'][s].tolist())}
+
+
+def _prepared(name):
+    return M.prepare_clip(skip_frames_without_gt=False, **ARGS[name])
+
+
+def test_rows_that_take_part_in_nothing(dev, host):
+    """Rows with id -1 and with id >= the id count in the middle of frames, on both sides, and an id count of the predictions that
+    no id reaches: the summary is that of the clip without those rows, and their similarities are 0."""
+    clip = _prepared('seed40')
+    rs = np.random.RandomState(9)
+    go, po = np.concatenate([[0], np.cumsum(clip['gt_rows'])]), np.concatenate([[0], np.cumsum(clip['pred_rows'])])
+    G, K = clip['n_gt_ids'], clip['n_pred_ids'] + 5
+    new = {k: [] for k in ('gt_boxes', 'gt_ids', 'pred_boxes', 'pred_ids')}
+    rows, junk = {'gt': [], 'pred': []}, {'gt': [], 'pred': []}
+    for t in range(clip['T']):
+        for side, off, n_ids in (('gt', go, G), ('pred', po, K)):
+            boxes, ids = clip[side + '_boxes'][off[t]:off[t + 1]], clip[side + '_ids'][off[t]:off[t + 1]]
+            k = len(ids)
+            extra = [(-1, k // 2), (n_ids, k // 2), (n_ids + 7, 0), (2 ** 31 - 1, k)][:2 + t % 3]     # (value, where): the middle, the ends
+            mark = np.zeros(k, bool)
+            for val, at in extra:
+                src = boxes[rs.randint(k)] if k else np.array([10., 10., 50., 80.], np.float32)        # on top of a real box: it would count
+                boxes, ids, mark = np.insert(boxes, at, src + rs.randn(4).astype(np.float32), 0), np.insert(ids, at, val), np.insert(mark, at, True)
+            new[side + '_boxes'].append(boxes); new[side + '_ids'].append(ids)
+            rows[side].append(len(ids)); junk[side].append(mark)
+    dirty = dict(clip, gt_rows=np.asarray(rows['gt']), pred_rows=np.asarray(rows['pred']), n_pred_ids=K,
+                 **{k: np.concatenate(v) for k, v in new.items()})
+    assert max(rows['gt']) <= 256 and sum(m.sum() for m in junk['gt']) >= 2 * clip['T'] and int(dirty['pred_ids'].max()) == 2 ** 31 - 1
+    assert not np.any((clip['pred_ids'] >= clip['n_pred_ids']))                                       # ids n_pred_ids .. K-1 own no row at all
+    block, go2, po2, gb, gi, pi, pb = _layout([dirty])
+    r = _score(dev, block, gb, gi, pi, pb)
+    want = host['seed40']
+    assert M._compare(_fields(r, 0, G), want, 1e-12) is None
+    at = 0
+    for t in range(clip['T']):
+        n, m = rows['gt'][t], rows['pred'][t]
+        sim = r['sim'][at:at + n * m].reshape(n, m)
+        at += n * m
+        assert np.all(sim[junk['gt'][t]] == 0) and np.all(sim[:, junk['pred'][t]] == 0), t
+        clean = M.iou_host(dirty['gt_boxes'][go2[t]:go2[t + 1]][~junk['gt'][t]], dirty['pred_boxes'][po2[t]:po2[t + 1]][~junk['pred'][t]], SETTINGS['max_iou'])
+        assert np.all(np.abs(sim[~junk['gt'][t]][:, ~junk['pred'][t]] - clean) <= 1e-12), t
+        assert np.all(r['rowsum'][go2[t]:go2[t + 1]][junk['gt'][t]] == 0) and np.all(r['colsum'][po2[t]:po2[t + 1]][junk['pred'][t]] == 0)
+    assert at == r['sim'].size
+
+
+def test_a_clip_of_zero_frames_between_two_others(dev):
+    a, b = _prepared('seed7'), _prepared('clear_book')
+    empty = dict(a, T=0, gt_rows=np.zeros(0, np.int64), pred_rows=np.zeros(0, np.int64), n_gt_ids=0, n_pred_ids=0, gt_ids=np.zeros(0, np.int32),
+                 pred_ids=np.zeros(0, np.int32), gt_boxes=np.zeros((0, 4), np.float32), pred_boxes=np.zeros((0, 4), np.float32))
+    three, two = _layout([a, empty, b]), _layout([a, b])
+    r3, r2 = _score(dev, three[0], *three[3:]), _score(dev, two[0], *two[3:])
+    for k in ('hota', 'clear', 'identity'):
+        assert r3[k].shape[0] == 3 and np.all(r3[k][1] == 0), k                                        # all zero, not merely small
+        assert r3[k][0].tobytes() == r2[k][0].tobytes() and r3[k][2].tobytes() == r2[k][1].tobytes(), k
+    for k in ('sim', 'rowsum', 'colsum'):
+        assert r3[k].tobytes() == r2[k].tobytes(), k
+    assert r2['clear'][:, 0].min() > 0 and np.isfinite(r3['hota']).all()                              # (CLR_TP of the neighbours)
+
+
+BAD_BOXES = [(np.nan, 0), (np.inf, 1), (-np.inf, 2), (np.nan, 3), (np.inf, 0), (-np.inf, 1), (np.nan, 2), (np.inf, 3), (-np.inf, 0), (np.nan, 1),
+             (np.inf, 2), (-np.inf, 3)]                                                                # every value in every coordinate
+
+
+def test_a_non_finite_box_is_similar_to_nothing(dev):
+    """A NaN or +-inf coordinate: similarity exactly 0 in that row or column, every other element byte-equal to the run without it."""
+    clip = _prepared('seed40')
+    block, go, po, gb, gi, pi, pb = _layout([clip])
+    clean = _score(dev, block, gb, gi, pi, pb, metrics=False)
+    gb2, pb2 = gb.copy(), pb.copy()
+    bad_g, bad_p = np.zeros(len(gb), bool), np.zeros(len(pb), bool)
+    frames = [t for t in range(clip['T']) if clip['gt_rows'][t] >= 2 and clip['pred_rows'][t] >= 2]
+    for i, (v, k) in enumerate(BAD_BOXES):                                                             # one row of either side in a frame of its own
+        t = frames[i]
+        g, p = go[t] + i % clip['gt_rows'][t], po[t] + (i + 1) % clip['pred_rows'][t]
+        gb2[g, k], pb2[p, k] = v, v
+        bad_g[g], bad_p[p] = True, True
+    got = _score(dev, block, gb2, gi, pi, pb2, metrics=False)
+    at, hit = 0, 0
+    for t in range(clip['T']):
+        n, m = int(clip['gt_rows'][t]), int(clip['pred_rows'][t])
+        a, b = got['sim'][at:at + n * m].reshape(n, m), clean['sim'][at:at + n * m].reshape(n, m)
+        at += n * m
+        rg, cp = bad_g[go[t]:go[t + 1]], bad_p[po[t]:po[t + 1]]
+        hit += int((b[rg] > 0).sum() + (b[:, cp] > 0).sum())
+        assert np.all(a[rg] == 0) and np.all(a[:, cp] == 0), (t, a[rg], a[:, cp])
+        assert a[~rg][:, ~cp].tobytes() == b[~rg][:, ~cp].tobytes(), t
+        with np.errstate(invalid='ignore'):
+            want = M.iou_host(gb2[go[t]:go[t + 1]], pb2[po[t]:po[t + 1]], SETTINGS['max_iou'])
+        assert np.all(np.abs(a - want) <= 1e-12) and np.all((a == 0) == (want == 0)), t           # (the host mirror says the same)
+    assert hit >= len(BAD_BOXES) and np.isfinite(got['sim']).all() and np.isfinite(got['rowsum']).all() and np.isfinite(got['colsum']).all()
 
 
 def test_skipping_frames_without_ground_truth(dev):
