@@ -1,6 +1,6 @@
 """BEV crowd mode (bev/main.py:184-258, bev/split2process.py): the long-image sliding window.
 
-CPU part: a numpy restatement of the crop plan and of the merge (boundary exclusion, per-crop projection, conf-based
+CPU part: the numpy restatement of the crop plan and of the merge (tests/crowd_cases.py: boundary exclusion, per-crop projection, conf-based
 suppression and outlier removal, the full-frame camera, the global suppression / outlier pass) matches the fixture that
 the reference's own process_long_image produced (tests/golden/bev_crowd.npz, scripts/make_golden_bev_crowd.py); the
 settings and the two C-ABI entry points exist.
@@ -11,119 +11,14 @@ than 256 rows in the global stage); BEV(--crowd) end to end equals the restateme
 device itself produced.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import bev_post_oracle as PO
-
-F32 = np.float32
-
-
-# ----------------------------------------------------------------------------------------------- numpy restatement
-def split_plan(h, w_pad, overlap):
-    """get_image_split_plan on the padded width (left, right, top, bottom; int32 truncation; the last crop keeps the previous
-    step's right)."""
-    n = int(np.ceil((w_pad / h - 1) / (1 - overlap))) + 1
-    step = (1 - overlap) * h
-    boxes, right = [], None
-    for i in range(n):
-        if i == n - 1:
-            left = w_pad - h
-        else:
-            left = step * i
-            right = left + h
-        boxes.append([left, right, 0, h])
-    return np.array(boxes).astype(np.int32)
-
-
-def frame_pad_info(h, w):
-    top = (w - h) // 2
-    return np.array([top, w - top, 0, w, h, w], F32)
-
-
-def crop_pad_info(ch, cw):
-    side = max(ch, cw)
-    top, left = (side - ch) // 2, (side - cw) // 2
-    return np.array([top, top + ch, left, left + cw, ch, cw], F32)
-
-
-def _margin(margins, x, thr):
-    if np.size(x):
-        margins.append(float(np.min(np.abs(np.asarray(x, np.float64) / float(thr) - 1))))
-
-
-def _suppress(pj_org, cam, conf, alive, thr, margins):
-    """conf-based suppressing_redundant_prediction_via_projection over the rows `alive` (row order); -> removed rows."""
-    idx = np.nonzero(alive)[0]
-    out = np.zeros(len(alive), bool)
-    if len(idx) < 2:
-        return out
-    p = pj_org[idx]
-    d = np.sqrt(((p[:, None] - p[None]) ** 2).sum(-1)).mean(-1).astype(F32)
-    sc = cam[idx, 0] * F32(2)
-    d = d / np.maximum(sc[:, None], sc[None])
-    _margin(margins, d[np.triu_indices(len(idx), 1)], F32(thr))
-    a, b = np.nonzero(np.triu(d < F32(thr), 1))
-    drop = np.where(conf[idx[a]] < conf[idx[b]], idx[a], idx[b])
-    out[drop] = True
-    return out
-
-
-def _outlier(trans, cam, alive, rel_thresh, scale_thresh, margins):
-    idx = np.nonzero(alive)[0]
-    out = np.zeros(len(alive), bool)
-    m = len(idx)
-    if m < 3:
-        return out
-    t = trans[idx]
-    dm = np.sqrt(((t[:, None] - t[None]) ** 2).sum(-1)).astype(F32)
-    mean = np.sort(dm, 1)[:, 1:-1].mean(1).astype(F32)
-    rel = mean / ((mean.sum() - mean) / F32(m - 1))
-    _margin(margins, rel[cam[idx, 0] < F32(scale_thresh)], F32(rel_thresh))
-    out[idx[(rel > F32(rel_thresh)) & (cam[idx, 0] < F32(scale_thresh))]] = True
-    return out
-
-
-def crowd_merge(crop_id, cam, conf, joints, crops, H, W, pad_length, nms=20., rel=1.6):
-    """Points 6-9 of process_long_image on per-row detections (rows crop-major).  -> dict(keep, cam_full, cam_trans, pj2d_org,
-    stages: how many rows each step removed, margin: the smallest relative distance of a compared value to its threshold)."""
-    cam, conf, joints = np.asarray(cam, F32), np.asarray(conf, F32), np.asarray(joints, F32)
-    K, N = len(crops), len(cam)
-    alive = np.ones(N, bool)
-    cam_full = cam.copy()
-    st = dict(excluded=0, crop_suppressed=0, crop_outliers=0, suppressed=0, outliers=0)
-    margins = []
-    for c in range(K):
-        rows = crop_id == c
-        l, r, t, b = [int(v) for v in crops[c]]
-        if c != K - 1:
-            hi = F32(1 - (r - int(crops[c + 1][0])) / H / 2)
-            _margin(margins, cam[rows, 2], hi)
-            ex = rows & (cam[:, 2] > hi)
-            st['excluded'] += int(ex.sum()); alive &= ~ex
-        if c >= 2:
-            lo = F32((int(crops[c - 1][1]) - l) / H / 2 - 1)
-            _margin(margins, cam[rows & alive, 2], lo)
-            ex = rows & alive & (cam[:, 2] < lo)
-            st['excluded'] += int(ex.sum()); alive &= ~ex
-        ch, cw = b - t, r - l
-        _, pj, tr = PO.project(joints, cam, [0, ch, 0, cw, ch, cw])
-        rm = _suppress(pj, cam, conf, rows & alive, nms * max(ch, cw) / 640, margins)
-        st['crop_suppressed'] += int(rm.sum()); alive &= ~rm
-        rm = _outlier(tr, cam, rows & alive, rel, 1, margins)
-        st['crop_outliers'] += int(rm.sum()); alive &= ~rm
-        scale = F32(max(r - l, b - t) / max(H, W))
-        shift = F32(np.mean([l - pad_length, r - pad_length]) / (W / 2) - 1)
-        cam_full[rows] = cam[rows] * scale
-        cam_full[rows, 2] += shift
-    _, pj, tr = PO.project(joints, cam_full, frame_pad_info(H, W))
-    rm = _suppress(pj, cam_full, conf, alive, nms * max(H, W) / 640, margins)
-    st['suppressed'] = int(rm.sum()); alive &= ~rm
-    rm = _outlier(tr, cam_full, alive, rel, 0.5, margins)
-    st['outliers'] = int(rm.sum()); alive &= ~rm
-    return {'keep': alive, 'cam_full': cam_full, 'cam_trans': tr, 'pj2d_org': pj, 'stages': st, 'margin': min(margins + [1.])}
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from crowd_cases import F32, crop_pad_info, crowd_merge, frame_pad_info, split_plan  # noqa: E402  (the numpy restatement)
 
 
 def _cases(golden_dir):
