@@ -168,7 +168,9 @@ typedef struct romp_op {
 
 typedef struct romp_net romp_net;
 
-/* buf_floats_per_image[i] = size of arena buffer i for ONE image, in floats. */
+/* buf_floats_per_image[i] = size of arena buffer i for ONE image, in floats.  What a stem, max-pool, split-K tail or fused op
+ * requires of its shape and strides alone is checked first, before the device is touched: such a program is refused with
+ * ROMP_EINVAL and the launcher's own message (romp_last_error) on a host without a device too. */
 int  romp_net_create(romp_net** out, const romp_op* ops_host, int n_ops,
                      const int64_t* buf_floats_per_image_host, int n_bufs, int max_batch);
 /* image (B,512,512,3) float 0..255 -> center_maps (B,64,64), params_maps (B,64,64,145).

@@ -60,12 +60,14 @@ int conv_trace_read(unsigned long long* dst_host, int max_words);
 bool conv_variant_valid(const romp_op& op, int variant);
 bool conv_variant_tunable(const romp_op& op, int variant);   // ... and offered to romp_net_autotune
 unsigned long long* conv_trace_arm(hipStream_t st);   // conv_mfma.hip: ROMP_CONV_TRACE stamp buffer, zeroed on `st` (nullptr: off)
-// The fused launchers' requirements on the ops alone (shapes, formats, packs -- nothing that depends on B or on device pointers):
-// romp_net_create runs them for every op of the kind, the launcher runs them again in front of its B-dependent ones.
+// The fused launchers' (and the stem / pool / split-K tail launchers') requirements on the ops alone (shapes, formats, packs -- nothing
+// that depends on B, on device pointers or on the device): romp_net_create runs them for every op of the kind BEFORE it touches the
+// device (a host without one still gets the named refusal), the launcher runs them again in front of its B-dependent ones.
 int check_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd);
 int check_bblock32(const romp_op& op1, const romp_op& op2), check_bblock32r(const romp_op& op1, const romp_op& op2), check_bblock64(const romp_op& op1, const romp_op& op2);
 int check_stem2(const romp_op& stem, const romp_op& op);
 int check_stem7p(const romp_op& op);
+int check_stem(const romp_op& op), check_stem7(const romp_op& op), check_maxpool(const romp_op& op), check_ksum(const romp_op& op);   // stem_fuse.hip
 int check_fuseup(const romp_op& op);
 int launch_seam1x1(const romp_op& opa, const romp_op& opb, const romp_op* opd, const float* m, const float* x, float* t, float* u, int B, const LaunchCtx& c);   // conv_h2x.hip
 int launch_bblock32r(const romp_op& op1, const romp_op& op2, const float* x, float* y, int B, int* queue, const LaunchCtx& c);  // conv_h2c32.hip

@@ -443,8 +443,9 @@ static int run_all(romp_net* n, const float* image, int B, float* center, float*
     return ROMP_OK;
 }
 
-// What a fused op's launcher requires of the ops alone: checked for every such op when the net is created.  (That the ops in front
-// of it are the NOPs it reads is run_op's to say; an op too early in the program for them is reported there.)
+// What a fused op's launcher -- and the stem, pool and split-K tail launchers -- require of the ops alone: checked for every such op
+// when the net is created, before the device is touched.  (That the ops in front of a fused op are the NOPs it reads is run_op's to
+// say; an op too early in the program for them is reported there.)
 static int check_fused_op(const romp_op* ops, int i) {
     const romp_op& op = ops[i];
     switch (op.kind) {
@@ -455,6 +456,10 @@ static int check_fused_op(const romp_op* ops, int i) {
             return check_seam1x1(ops[i - 1], op, (op.flags & ROMP_OPF_SEAM_DS) ? &ops[i - 2] : nullptr);
         case ROMP_OP_STEM2: return i > 0 ? check_stem2(ops[i - 1], op) : ROMP_OK;
         case ROMP_OP_STEM7P: return check_stem7p(op);
+        case ROMP_OP_STEM: return check_stem(op);
+        case ROMP_OP_STEM7: return check_stem7(op);
+        case ROMP_OP_MAXPOOL: return check_maxpool(op);
+        case ROMP_OP_KSUM: return check_ksum(op);
         case ROMP_OP_FUSEUP: return check_fuseup(op);
         default: return ROMP_OK;
     }
@@ -468,11 +473,11 @@ const char* romp_last_error(void) { return romp::g_err; }
 int romp_net_create(romp_net** out, const romp_op* ops_host, int n_ops, const int64_t* buf_floats, int n_bufs,
                     int max_batch) {
     ROMP_REQUIRE(out && ops_host && n_ops > 0 && n_bufs >= 0 && max_batch > 0, "romp_net_create: bad arguments");
-    { const int rc = device_init(); if (rc) return rc; }
-    for (int i = 0; i < n_ops; ++i) {
+    for (int i = 0; i < n_ops; ++i) {                          // (host work only: a refusal needs no device)
         const int rc = check_fused_op(ops_host, i);
         if (rc) return rc;
     }
+    { const int rc = device_init(); if (rc) return rc; }
     romp_net* n = new romp_net();
     n->ops.assign(ops_host, ops_host + n_ops);
     n->buf_floats.assign(buf_floats, buf_floats + n_bufs);
@@ -944,6 +949,7 @@ void romp_net_destroy(romp_net* n) {
 int romp_conv_forward(const romp_op* op, const float* in, const float* res, float* out, int B, int mode, int variant,
                       void* stream) {
     ROMP_REQUIRE(op && in && out && B > 0, "romp_conv_forward: bad arguments");
+    if (op->kind == ROMP_OP_STEM) { const int rc = check_stem(*op); if (rc) return rc; }     // (as romp_net_create: refused before the device is touched)
     { const int rc = device_init(); if (rc) return rc; }
     const LaunchCtx c{(hipStream_t)stream, nullptr, 0};    // a stand-alone layer belongs to no net: nothing to report to, no cap
     if (op->kind == ROMP_OP_STEM) return launch_stem(*op, in, out, B, c);

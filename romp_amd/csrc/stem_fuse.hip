@@ -238,17 +238,23 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(StemParams p) {
     sat_report(p.sat, sat_mx);
 }
 
-int launch_stem(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+// What launch_stem requires of the op alone (common.h: romp_net_create and romp_conv_forward ask before they touch the device)
+int check_stem(const romp_op& op) {
     ROMP_REQUIRE(op.Cin == 3 && op.Cout == 64 && op.ksize == 3 && op.stride == 2, "stem: expects 3->64 k3 s2");
     ROMP_REQUIRE(op.H % 32 == 0 && op.W % 32 == 0, "stem: input %dx%d must be a multiple of 32", op.H, op.W);
     ROMP_REQUIRE((op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0, "stem: output channels must be float4 aligned");
+    ROMP_REQUIRE(op.out_fmt != ROMP_FMT_H2 || ((op.out_cstride | op.out_coff) & 7) == 0, "stem: H2 output needs octet-aligned channels");
+    return ROMP_OK;
+}
+
+int launch_stem(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+    { const int rc = check_stem(op); if (rc) return rc; }
     StemParams p;
     p.image = image; p.w = op.weight; p.scale = op.scale; p.shift = op.shift; p.out = out;
     p.H = op.H; p.W = op.W; p.Ho = op.H / 2; p.Wo = op.W / 2;
     p.out_cs = op.out_cstride; p.out_co = op.out_coff;
     p.out_h2 = op.out_fmt == ROMP_FMT_H2; p.act_scale = ldexpf(1.f, op.act_shift);
     p.sat = c.sat;
-    ROMP_REQUIRE(!p.out_h2 || ((op.out_cstride | op.out_coff) & 7) == 0, "stem: H2 output needs octet-aligned channels");
     p.tiles_x = p.Wo / 16; p.tiles_y = p.Ho / 16;
     // ROMP_OPF_STEM_VALU (plan.Program.stem): the float32 VALU kernel for the H2 output too -- set by env ROMP_STEM=valu (A/B runs,
     // tests) and whenever 256 |w| would leave the fp16 pieces of the MFMA form (its 16x input / 256x weight scales are internal to
@@ -337,10 +343,15 @@ __global__ __launch_bounds__(256) void stem7_conv_kernel(Stem7Params p) {
     }
 }
 
-int launch_stem7(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+int check_stem7(const romp_op& op) {
     ROMP_REQUIRE(op.Cin == 3 && op.Cout == 64 && op.ksize == 7 && op.stride == 2, "stem7: expects 3->64 k7 s2");
     ROMP_REQUIRE(op.H % 32 == 0 && op.W % 32 == 0, "stem7: input %dx%d must be a multiple of 32", op.H, op.W);
     ROMP_REQUIRE((op.out_cstride & 3) == 0 && (op.out_coff & 3) == 0, "stem7: output channels must be float4 aligned");
+    return ROMP_OK;
+}
+
+int launch_stem7(const romp_op& op, const float* image, float* out, int B, const LaunchCtx& c) {
+    { const int rc = check_stem7(op); if (rc) return rc; }
     Stem7Params p;
     p.image = image; p.w = op.weight; p.scale = op.scale; p.shift = op.shift; p.out = out;
     p.H = op.H; p.W = op.W; p.Ho = op.H / 2; p.Wo = op.W / 2;
@@ -376,9 +387,14 @@ __global__ void maxpool3s2_kernel(const float* __restrict__ in, int H, int W, in
     }
 }
 
+int check_maxpool(const romp_op& op) {
+    ROMP_REQUIRE((op.Cin & 3) == 0 && (op.in_cstride & 3) == 0 && (op.out_cstride & 3) == 0 && !(op.H & 1) && !(op.W & 1), "maxpool: bad shape");
+    return ROMP_OK;
+}
+
 int launch_maxpool(const romp_op& op, const float* in, float* out, int B, const LaunchCtx& c) {
-    ROMP_REQUIRE(in && out && (op.Cin & 3) == 0 && (op.in_cstride & 3) == 0 && (op.out_cstride & 3) == 0 && !(op.H & 1) && !(op.W & 1),
-                 "maxpool: bad shape");
+    ROMP_REQUIRE(in && out, "maxpool: null buffer");
+    { const int rc = check_maxpool(op); if (rc) return rc; }
     const size_t total = (size_t)B * (op.H / 2) * (op.W / 2) * (op.Cin / 4);
     size_t blocks = (total + 255) / 256;
     if (blocks > 16384) blocks = 16384;
@@ -570,10 +586,16 @@ __global__ __launch_bounds__(256) void ksum_kernel(KsumParams p) {
     if (p.out_h2) sat_report(p.sat, sat_mx);
 }
 
+int check_ksum(const romp_op& op) {
+    ROMP_REQUIRE(op.groups >= 1 && (op.Cout & 7) == 0 && op.in_cstride == op.groups * op.Cout, "ksum: partials must be %d x %d channels", op.groups, op.Cout);
+    ROMP_REQUIRE(((op.out_cstride | op.out_coff) & 7) == 0 && (op.res_buf == ROMP_BUF_NONE || ((op.res_cstride | op.res_coff) & 7) == 0), "ksum: channels must come in octets");
+    return ROMP_OK;
+}
+
 int launch_ksum(const romp_op& op, const float* partial, const float* res, float* out, int B, const LaunchCtx& c) {
     ROMP_REQUIRE(partial && out && op.scale && op.shift, "ksum: null buffer");
-    ROMP_REQUIRE(op.groups >= 1 && (op.Cout & 7) == 0 && op.in_cstride == op.groups * op.Cout, "ksum: partials must be %d x %d channels", op.groups, op.Cout);
-    ROMP_REQUIRE(((op.out_cstride | op.out_coff) & 7) == 0 && (!res || ((op.res_cstride | op.res_coff) & 7) == 0), "ksum: channels must come in octets");
+    { const int rc = check_ksum(op); if (rc) return rc; }
+    ROMP_REQUIRE(!res || ((op.res_cstride | op.res_coff) & 7) == 0, "ksum: channels must come in octets");
     KsumParams p;
     p.part = partial; p.res = res; p.scale = (const float*)op.scale; p.shift = (const float*)op.shift; p.out = out;
     p.G = op.groups; p.C = op.Cout; p.C8 = op.Cout / 8; p.part_cs = op.in_cstride;
