@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libromp_hip.so')
 # (heaviest translation units first: the thread pool below starts them in this order and the link waits for the slowest)
 SOURCES = ['conv_h2.hip', 'conv_h2c.hip', 'conv_h2c32.hip', 'conv_f32.hip', 'conv_h2d.hip', 'conv_h2b.hip', 'conv_h2r.hip',
-           'conv_h2s.hip', 'conv_mfma.hip', 'conv_h2k.hip', 'conv_h2g.hip', 'conv_h2x.hip', 'conv_fup.hip', 'stem_fuse.hip', 'stem2.hip', 'stem7p.hip', 'net.hip', 'parse.hip', 'smpl.hip', 'smpl_grad.hip', 'bev.hip', 'fit.hip', 'fit_priors.hip', 'fit_clip.hip',
+           'conv_h2s.hip', 'conv_mfma.hip', 'conv_h2k.hip', 'conv_h2g.hip', 'conv_h2x.hip', 'conv_fup.hip', 'stem_fuse.hip', 'stem2.hip', 'stem7p.hip', 'net.hip', 'parse.hip', 'smpl.hip', 'smpl_grad.hip', 'bev.hip', 'fit.hip', 'fit_priors.hip', 'fit_clip.hip', 'fit_scene.hip',
            'post.hip', 'crowd.hip', 'render.hip', 'temporal.hip', 'eval.hip', 'rh.hip', 'track.hip', 'mot.hip']
 # optional: the bf16x3 family (`--conv_math bf16x3`; no committed variant table selects it; a minute of compile time): ROMP_WITH_BX3=1
 OPTIONAL_BX3 = 'conv_bx3.hip'
@@ -43,7 +43,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=None, objdir=None, wit
     sources = SOURCES + ([OPTIONAL_BX3] if with_bx3 else [])
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + \
               [os.path.join(HERE, '..', 'include', h) for h in ('romp_hip.h', 'romp_hip_views.h', 'romp_hip_maps.h', 'romp_hip_eval.h', 'romp_hip_rh.h',
-                                                              'romp_hip_canvases.h', 'romp_hip_smpl_grad.h', 'romp_hip_fit.h', 'romp_hip_fit_priors.h', 'romp_hip_fit_clip.h', 'romp_hip_track.h', 'romp_hip_mot.h')]
+                                                              'romp_hip_canvases.h', 'romp_hip_smpl_grad.h', 'romp_hip_fit.h', 'romp_hip_fit_priors.h', 'romp_hip_fit_clip.h', 'romp_hip_fit_scene.h', 'romp_hip_track.h', 'romp_hip_mot.h')]
     objdir = objdir or os.path.join(HERE, 'build')
     lib = lib or LIB
     os.makedirs(objdir, exist_ok=True)

@@ -28,6 +28,11 @@ Given the ``links`` of a tracked clip (``romp_amd.clip.clip_links``) ``KeypointF
 track in the neighbouring frames: velocity and acceleration terms on joints, camera and betas and a first-order term on the
 joint rotations (include/romp_hip_fit_clip.h, csrc/fit_clip.hip), two more launches per step.  ``romp_amd.clip`` holds the
 links, the autograd nodes of these terms and ``refine_clip``.
+
+Given the ``scene`` tables of a ``forward_batch`` (``romp_amd.scene.scene_groups``) ``KeypointFitter`` ties the persons of one
+image together: a depth-order term from depth-layer labels and a sphere-proxy collision term between different persons
+(include/romp_hip_fit_scene.h, csrc/fit_scene.hip), one more launch per step.  ``romp_amd.scene`` holds the tables, the sphere
+table, the autograd nodes of these terms and ``refine_scene``.
 """
 import ctypes as C
 
@@ -197,6 +202,21 @@ def _temporal(segs, links, N, loss, poses=None, joint_w=None, w_rot=0., sigma_ro
                                            int(accumulate), L.ptr(loss), L.ptr(history), int(row), L.stream_ptr(dev)))
 
 
+def _fit_scene(joints, cam, mode, groups, depth_ids, w_depth, thresh, kind, table, radius_scale, w_col, term_w, gj, acc_j, gc, acc_c,
+               loss, history=None, row=0):
+    """romp_fit_scene: groups = (offsets, members) on the device, table a ctypes array of ``L.SceneSphere`` (or None: no
+    collision term; joints and gj may be None then), depth_ids int32 (N,) or None (no depth term)."""
+    dev = cam.device
+    if dev.type != 'cuda':
+        raise L.RompHipError('the scene terms run on the HIP device only (no CPU fallback); move the tensors to "cuda:N"')
+    N, J = cam.shape[0], 0 if joints is None else joints.shape[1]
+    with torch.cuda.device(dev):
+        L.check(L.load().romp_fit_scene(L.ptr(joints), int(N), int(J), L.ptr(cam), int(mode), L.ptr(groups[0]), L.ptr(groups[1]),
+                                        L.ptr(depth_ids), float(w_depth), float(thresh), int(kind), table,
+                                        0 if table is None else len(table), L.ptr(radius_scale), float(w_col), L.ptr(term_w), L.ptr(gj),
+                                        int(acc_j), L.ptr(gc), int(acc_c), L.ptr(loss), L.ptr(history), int(row), L.stream_ptr(dev)))
+
+
 def _pair(w, name):
     """A (velocity, acceleration) weight pair; a number stands for the velocity weight alone."""
     vel, acc = (w, 0.) if np.ndim(w) == 0 else w
@@ -330,12 +350,22 @@ class KeypointFitter(object):
     (24,) or None = ones), first order, free of the axis-angle wrap.  ``sigma_smooth`` > 0 makes rho Geman-McClure for all of
     them.  With any of them on a step gains two launches (joints and camera before ``smpl_backward``, betas and rotations
     after it) and the result ``smooth_history`` (steps + 1, N, L), unweighted: (vel, acc) columns for joints, cam and betas,
-    then one for the rotations, each present when its term is on."""
+    then one for the rotations, each present when its term is on.
+
+    Scene terms (include/romp_hip_fit_scene.h), all off by default; they act when ``fit`` is given ``scene``, the (offsets,
+    members) row tables of ``romp_amd.scene.scene_groups``, and tie the persons of one image together.  ``w_depth_order``
+    weighs the depth-order term of ``romp_amd.scene.depth_order_loss`` on the ``depth_ids`` given to ``fit`` (``depth_loss_type``
+    'piecewise' or 'log', ``dist_thresh``); ``w_collision`` weighs ``romp_amd.scene.collision_loss`` with the table ``spheres``
+    (a ``BodySpheres``; None = ``body_spheres`` of the layer) and ``fit``'s ``radius_scale``.  The translation of a row is cam
+    with the perspective camera and 2 (c1 / s, c2 / s, 1 / s) with the weak one.  With either on a step gains one launch
+    (after the 2-D, 3-D and temporal ones, before ``smpl_backward``) and the result ``scene_history`` (steps + 1, N, 2),
+    unweighted: (depth, collision)."""
 
     def __init__(self, smpl, camera='weak', steps=30, lr=0.02, sigma=0., w_betas=1e-4, w_pose=1e-4, root_align=False,
                  focal=443.4, half=256., betas=(0.9, 0.999), eps=1e-8, pose_prior=None, w_gmm=0., w_angle=0., w_3d=1., sigma_3d=0.,
                  align_inds=None, w_smooth_pose=0., joint_w=None, w_smooth_joints=(0., 0.), smooth_joint_inds=None,
-                 w_smooth_cam=(0., 0.), w_smooth_betas=0., sigma_smooth=0.):
+                 w_smooth_cam=(0., 0.), w_smooth_betas=0., sigma_smooth=0., w_depth_order=0., depth_loss_type='piecewise',
+                 dist_thresh=0.3, w_collision=0., spheres=None):
         self.smpl, self.camera, self.mode = smpl, camera, _mode(camera)
         self.steps, self.lr, self.sigma = int(steps), float(lr), float(sigma)
         self.w_betas, self.w_pose, self.root_align = w_betas, w_pose, bool(root_align)
@@ -352,6 +382,13 @@ class KeypointFitter(object):
         if not (self.w_smooth_pose >= 0 and self.w_smooth_betas >= 0):
             raise ValueError('w_smooth_pose and w_smooth_betas must not be negative')
         self.smooth_on = max(self.w_smooth_pose, self.w_smooth_betas, *(self.w_smooth_joints + self.w_smooth_cam)) > 0
+        self.w_depth_order, self.w_collision, self.dist_thresh = float(w_depth_order), float(w_collision), float(dist_thresh)
+        self.depth_loss_type, self.spheres = depth_loss_type, spheres
+        if not (self.w_depth_order >= 0 and self.w_collision >= 0 and self.dist_thresh >= 0):
+            raise ValueError('w_depth_order, w_collision and dist_thresh must not be negative')
+        if str(depth_loss_type).lower() not in ('piecewise', 'log'):
+            raise ValueError("depth_loss_type must be 'piecewise' or 'log', not %r" % (depth_loss_type,))
+        self.scene_on = max(self.w_depth_order, self.w_collision) > 0
 
     @staticmethod
     def _weights(w, cols, dev, free=0):
@@ -367,19 +404,28 @@ class KeypointFitter(object):
             raise ValueError('a prior weight vector needs %d entries, got %d' % (cols, out.numel()))
         return out
 
-    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
+    def start(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None,
+              scene=None, depth_ids=None, radius_scale=None, fixed=None):
         """The buffers of one fit and its two halves of a step (``_FitRun``); ``fit`` drives it."""
-        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links)
+        return _FitRun(self, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links, scene, depth_ids,
+                       radius_scale, fixed)
 
-    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
+    def fit(self, betas0, poses0, cam0, kp2d, conf=None, joint_inds=None, joints3d=None, conf3d=None, joint_inds3d=None, links=None,
+            scene=None, depth_ids=None, radius_scale=None, fixed=None):
         """betas0 (N,n_betas), poses0 (N,72), cam0 (N,3) (`cam` or `cam_trans`, by the camera), kp2d (N,K,2) in the normalised
         frame (None: no 2-D term, joints3d is needed then), conf (N,K) or None, joint_inds: K joint indices of the 71 or None
         (= the first K); joints3d (N,K3,3) or None, conf3d (N,K3) or None, joint_inds3d likewise.  The inputs are not changed.
         -> dict(betas, poses, cam, verts, joints, loss_history (steps + 1, N)), device tensors; nothing is downloaded; with the
         prior terms on also prior_history (steps + 1, N, 2), with joints3d also loss3d_history (steps + 1, N).
         links: (prev, next), the row tables of ``romp_amd.clip.clip_links``, or None; with links and a smoothness weight above
-        zero the rows of a track are fitted together and smooth_history (steps + 1, N, L) is returned too."""
-        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links)
+        zero the rows of a track are fitted together and smooth_history (steps + 1, N, L) is returned too.
+        scene: (offsets, members), the row tables of ``romp_amd.scene.scene_groups``, or None; with scene and a scene weight above
+        zero the persons of an image are fitted together and scene_history (steps + 1, N, 2) is returned too.  depth_ids (N,)
+        integer depth layers, -1 = unlabelled (None: no depth term); radius_scale (N,) or None = ones.  fixed: (joints (F,71,3),
+        cam (F,3)) or None: F further rows that take part in the scenes but are not fitted (persons on another layer); the
+        tables, depth_ids and radius_scale then cover N + F rows, the fitted ones first."""
+        run = self.start(betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d, conf3d, joint_inds3d, links, scene, depth_ids,
+                         radius_scale, fixed)
         for s in range(self.steps):
             run.evaluate(s)
             run.update(s + 1)
@@ -390,6 +436,8 @@ class KeypointFitter(object):
                'loss_history': run.history}
         if run.smooth_on:
             out['smooth_history'] = torch.cat([h for h in (run.hist_eval, run.hist_upd) if h is not None], 2)
+        if run.scene_on:
+            out['scene_history'] = run.hist_scene[:, :run.N]
         if run.prior_on:
             out['prior_history'] = run.prior_history
         if run.targets3d is not None:
@@ -404,9 +452,11 @@ class _FitRun(object):
     romp_fit_joints3d onto the same gradients; with a prior term on update runs romp_fit_pose_prior between its two launches
     (losses into prior_history[the row of the last evaluate]).  With links and a smoothness term on, evaluate ends with
     romp_fit_temporal over the joints and the camera, onto the gradients smpl_backward and romp_fit_adam read, and update runs
-    it over the betas and the rotations between smpl_backward and romp_fit_adam."""
+    it over the betas and the rotations between smpl_backward and romp_fit_adam.  With scene tables and a scene term on,
+    evaluate ends with romp_fit_scene over the joints and the camera, onto the same gradients."""
 
-    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d=None, conf3d=None, joint_inds3d=None, links=None):
+    def __init__(self, fitter, betas0, poses0, cam0, kp2d, conf, joint_inds, joints3d=None, conf3d=None, joint_inds3d=None, links=None,
+                 scene=None, depth_ids=None, radius_scale=None, fixed=None):
         self.fitter, smpl = fitter, fitter.smpl
         self.dev = dev = smpl.shapedirs.device
         self.ctx = smpl._context()                                   # raises without a HIP device
@@ -444,13 +494,16 @@ class _FitRun(object):
         if self.prior_on:
             self.loss_prior, self.prior_history = torch.empty(N, 2, **f32), torch.empty(fitter.steps + 1, N, 2, **f32)
         self.row = 0
+        self.scene_on = scene is not None and (fitter.w_collision > 0 or (fitter.w_depth_order > 0 and depth_ids is not None))
+        if self.scene_on:                                            # before anything below takes the buffers' addresses
+            self._scene_setup(scene, depth_ids, radius_scale, fixed, f32)
         self.smooth_on = links is not None and fitter.smooth_on
         self.seg_eval = self.seg_upd = self.hist_eval = self.hist_upd = None
         if self.smooth_on:
             self._smooth_setup(links, f32)
         # A step is bound by the host issuing its launches, so a fit with nothing but the old four entries keeps the old two
         # methods, test for test (profiles/fit_prior_latency.txt holds that step against the parent commit's).
-        if self.kp2d is not None and self.targets3d is None and not self.prior_on and not self.smooth_on:
+        if self.kp2d is not None and self.targets3d is None and not self.prior_on and not self.smooth_on and not self.scene_on:
             self.evaluate, self.update = self._evaluate_2d, self._update_2d
         self.state = torch.zeros(2, N * (nb + 72 + 3), **f32)        # Adam's m and v of the three tensors
         self.poses_ref = self.poses.clone()
@@ -465,6 +518,52 @@ class _FitRun(object):
             self.segs[i] = L.FitSegment(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
                                         None if ref is None or w is None else ref.data_ptr(), None if w is None else w.data_ptr(),
                                         N, p.shape[1])
+
+    def _scene_setup(self, scene, depth_ids, radius_scale, fixed, f32):
+        """The tables and buffers of the romp_fit_scene launch of a step.  With F fixed rows the joints, the camera and their
+        gradients become the first N rows of (N + F)-row buffers whose tail holds the fixed rows, so one launch reads both."""
+        from . import scene as S                                     # (scene imports this module: resolved at call time)
+        BodySpheres, _groups, _kind, body_spheres = S.BodySpheres, S._groups, S._kind, S.body_spheres
+        f, N, dev = self.fitter, self.N, self.dev
+        NT = N
+        if fixed is not None:
+            fj, fc = (_f32(t, dev) for t in fixed)
+            if fj.dim() != 3 or fj.shape[1:] != (71, 3) or fc.shape != (fj.shape[0], 3):
+                raise ValueError('fit: fixed = (joints (F,71,3), cam (F,3))')
+            NT = N + fj.shape[0]
+            self.joints_all, self.cam_all = torch.cat([self.joints, fj]), torch.cat([self.cam, fc])
+            self.gj_all, self.gc_all = torch.zeros(NT, 71, 3, **f32), torch.zeros(NT, 3, **f32)
+            self.joints, self.cam, self.gj, self.gc = self.joints_all[:N], self.cam_all[:N], self.gj_all[:N], self.gc_all[:N]
+        else:
+            self.joints_all, self.cam_all, self.gj_all, self.gc_all = self.joints, self.cam, self.gj, self.gc
+        self.scene = _groups(scene, NT, dev)
+        self.depth_ids = None
+        if depth_ids is not None and f.w_depth_order > 0:
+            self.depth_ids = torch.as_tensor(depth_ids).to(dev).to(torch.int32).contiguous()
+            if self.depth_ids.shape != (NT,):
+                raise ValueError('fit: depth_ids needs one entry per row (%d), got %s' % (NT, tuple(self.depth_ids.shape)))
+        self.sphere_table = None
+        if f.w_collision > 0:
+            spheres = body_spheres(f.smpl) if f.spheres is None else f.spheres
+            if not isinstance(spheres, BodySpheres) or not len(spheres):
+                raise ValueError('spheres must be a non-empty romp_amd.scene.BodySpheres')
+            self.sphere_table = spheres.table()
+        self.radius_scale = None if radius_scale is None or self.sphere_table is None else _f32(radius_scale, dev).reshape(-1)
+        if self.radius_scale is not None and self.radius_scale.shape != (NT,):
+            raise ValueError('fit: radius_scale needs one entry per row (%d)' % NT)
+        self.scene_kind = _kind(f.depth_loss_type)
+        self.loss_scene, self.hist_scene = torch.empty(NT, 2, **f32), torch.empty(f.steps + 1, NT, 2, **f32)
+
+    def _scene(self, row):
+        """romp_fit_scene on the current joints and camera: the losses into scene_history[row], the gradients onto those of the
+        joints (always written earlier in the step) and into or onto that of the camera."""
+        f = self.fitter
+        cam_written = self.kp2d is not None or (self.targets3d is not None and f.mode == 1) or \
+            (self.seg_eval is not None and max(f.w_smooth_cam) > 0)
+        _fit_scene(self.joints_all if self.sphere_table is not None else None, self.cam_all, f.mode, self.scene, self.depth_ids,
+                   f.w_depth_order, f.dist_thresh, self.scene_kind, self.sphere_table, self.radius_scale, f.w_collision, None,
+                   self.gj_all if self.sphere_table is not None else None, 1, self.gc_all, int(cam_written), self.loss_scene,
+                   self.hist_scene, row)
 
     def _smooth_setup(self, links, f32):
         """The segment tables and loss buffers of the two romp_fit_temporal launches of a step."""
@@ -541,6 +640,8 @@ class _FitRun(object):
                       f.w_3d, self.loss3d, self.gj, self.gc if cam else None, int(self.kp2d is not None), self.history3d, row)
         if self.seg_eval is not None:
             _temporal(self.seg_eval, self.links, self.N, self.loss_eval, history=self.hist_eval, row=row)
+        if self.scene_on:
+            self._scene(row)
         self.row = row
 
     def update(self, step):
@@ -593,9 +694,11 @@ def refine_outputs(model, outputs, kp2d_org, conf=None, joint_inds=None, pad_inf
     return _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf3d, joint_inds3d, None, fit_args)
 
 
-def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf3d, joint_inds3d, link_fn, fit_args):
+def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf3d, joint_inds3d, link_fn, fit_args, scene_fn=None):
     """``refine_outputs``; link_fn(rows) -> the (prev, next) of the rows fitted together (rows: device indices into the dict's
-    persons, None = all of them), or link_fn = None for unrelated rows (``romp_amd.clip.refine_clip`` supplies it)."""
+    persons, None = all of them), or link_fn = None for unrelated rows (``romp_amd.clip.refine_clip`` supplies it).
+    scene_fn(rows, new) -> the scene arguments of ``KeypointFitter.fit`` for those rows (new: the BEV results so far, its
+    joints and cam_trans the network's for the rows not fitted yet), or None (``romp_amd.scene.refine_scene`` supplies it)."""
     from .post_parser import body_mesh_projection2image
     parser = getattr(model, 'smpl_parser', None)
     if parser is None:
@@ -607,14 +710,15 @@ def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf
     kp = None if kp2d_org is None else keypoints_to_input_frame(_f32(kp2d_org, dev), pad)
     conf = None if conf is None else _f32(conf, dev)
     joints3d, conf3d = (None if t is None else _f32(t, dev) for t in (joints3d, conf3d))
-    extra = ('prior_history', 'loss3d_history', 'smooth_history')
+    extra = ('prior_history', 'loss3d_history', 'smooth_history', 'scene_history')
+    scene_of = (lambda rows, new: {}) if scene_fn is None else scene_fn
     N = betas.shape[0]
     out = dict(outputs)
     links_of = (lambda rows: None) if link_fn is None else link_fn
     if not is_bev:
         fitter = KeypointFitter(parser.smpl_model, camera='weak', **dict(dict(root_align=model.settings.root_align), **fit_args))
         res = fitter.fit(betas, thetas, _f32(outputs['cam'], dev), kp, conf, joint_inds, joints3d, conf3d, joint_inds3d,
-                         links=links_of(None))
+                         links=links_of(None), **scene_of(None, None))
         proj = body_mesh_projection2image(res['joints'], res['cam'], input2org_offsets=pad)
         out.update({'smpl_betas': res['betas'], 'smpl_thetas': res['poses'], 'cam': res['cam'], 'cam_trans': proj['cam_trans'],
                     'verts': res['verts'], 'joints': res['joints'], 'pj2d': proj['pj2d'], 'pj2d_org': proj['pj2d_org'],
@@ -630,6 +734,8 @@ def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf
     new = {'smpl_betas': betas.clone(), 'smpl_thetas': thetas.clone(), 'cam_trans': trans.clone(),
            'verts': torch.empty(N, 6890, 3, device=dev), 'joints': torch.empty(N, 71, 3, device=dev),
            'fit_loss': torch.empty(N, 2, device=dev)}
+    if scene_fn is not None:                                          # a group's fixed rows: the network's joints until they are fitted
+        new['joints'] = _f32(outputs['joints'], dev).clone()
     pick = lambda t, rows: None if t is None else t[rows]
     for layer, rows, nb in groups:
         if rows.numel() == 0:
@@ -638,7 +744,7 @@ def _refine(model, outputs, kp2d_org, conf, joint_inds, pad_info, joints3d, conf
         group_args = dict(args, pose_prior=None) if layer is parser.smil_model else args
         res = KeypointFitter(layer, camera='perspective', **group_args).fit(
             betas[rows][:, :nb], thetas[rows], trans[rows], pick(kp, rows), pick(conf, rows), joint_inds, pick(joints3d, rows),
-            pick(conf3d, rows), joint_inds3d, links=links_of(rows))
+            pick(conf3d, rows), joint_inds3d, links=links_of(rows), **scene_of(rows, new))
         new['smpl_betas'][rows, :nb] = res['betas']
         for key in extra:                                             # (steps + 1, n, ...) of this group into (steps + 1, N, ...)
             if key in res:

@@ -57,6 +57,11 @@ class ClipSegment(C.Structure):
                 ('w_acc', C.c_float), ('sigma_vel', C.c_float), ('sigma_acc', C.c_float), ('accumulate', C.c_int32)]
 
 
+class SceneSphere(C.Structure):
+    """Mirror of `struct romp_scene_sphere` (include/romp_hip_fit_scene.h): one proxy sphere of a romp_fit_scene call."""
+    _fields_ = [('p', C.c_int32), ('q', C.c_int32), ('a', C.c_float), ('r', C.c_float)]
+
+
 _lib = None
 
 
@@ -153,6 +158,8 @@ def load():
                                         i32, vp, i32, vp]),
         'romp_fit_temporal': (C.c_int, [C.POINTER(ClipSegment), i32, vp, vp, i32, vp, vp, vp, f, f, vp, i32, vp, vp, i32, vp]),
         'romp_clip_accel': (C.c_int, [vp, i32, i32, vp, vp, i32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp]),
+        'romp_fit_scene': (C.c_int, [vp, i32, i32, vp, i32, vp, vp, vp, f, f, i32, C.POINTER(SceneSphere), i32, vp, f, vp, vp, i32, vp, i32,
+                                     vp, vp, i32, vp]),
         'romp_track_state_bytes': (C.c_int, [i32]),
         'romp_track_init': (C.c_int, [vp, i32, i32, f, f, C.c_double, i32, C.c_double, vp]),
         'romp_track_frames': (C.c_int, [vp, vp, vp, C.POINTER(C.c_int32), i32, vp, vp, vp, vp, vp, i32, vp]),
@@ -209,6 +216,8 @@ FIT_EXPORTS = ['romp_fit_reproject', 'romp_fit_adam']
 FIT_PRIOR_EXPORTS = ['romp_fit_pose_prior', 'romp_fit_joints3d']
 # include/romp_hip_fit_clip.h: temporal smoothness terms over the links of a tracked clip for the same fit, and the acceleration metric
 FIT_CLIP_EXPORTS = ['romp_fit_temporal', 'romp_clip_accel']
+# include/romp_hip_fit_scene.h: depth-order and inter-person collision terms over the scenes (images) of the same fit
+FIT_SCENE_EXPORTS = ['romp_fit_scene']
 # include/romp_hip_track.h: ByteTrack-3D association on the device (the tracker, its assignment alone, the track lists) and the
 # OneEuro filters over what it reported
 TRACK_EXPORTS = ['romp_track_state_bytes', 'romp_track_init', 'romp_track_frames', 'romp_track_assign', 'romp_track_list',
